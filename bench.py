@@ -1,7 +1,12 @@
 """Headline benchmark: volumes/s for Compose[Affine, ElasticDeformation, BiasField, Blur, Noise] on 256^3 float32.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line.  ``--full`` adds everything else the line
+can carry (the roofline's per-launch timing, the other noise / resampling modes, multi-stream, the other configurations,
+the stock-ATen and CPU baselines, the measured HBM ceiling).  ``--dump-outputs DIR`` writes what the last timed step
+returned as ``DIR/<name>.npy`` (see ``dump_outputs``).
 
 One "step" = one pass of the Compose over one device-resident SubjectsBatch of
 `--batch` (default 8) synthetic 1x256^3 float32 volumes per GPU with per-instance
@@ -220,6 +225,36 @@ def aten_baseline(size: int, batch: int, device, steps: int = 3) -> dict:
     }
 
 
+DUMP_BUDGET_BYTES = 32 * 2**20  # the image's voxels written by --dump-outputs at most, all ranks together (a seeded sample above it)
+DUMP_SAMPLE_SEED = 20261016
+
+
+def dump_outputs(out, directory: str, suffix: str = "", budget_bytes: int = DUMP_BUDGET_BYTES) -> dict:
+    """What the timed path handed back in its last step, as ``.npy`` files: ``t1.npy`` (float32) holds the image's voxels —
+    the whole ``(B, 1, D, H, W)`` tensor when it fits *budget_bytes*, otherwise the same fixed, seeded sample of
+    voxel positions (sorted flat indices) of every volume, ``(B, n)`` — and ``t1_affine.npy`` (float64) the ``(B, 4, 4)``
+    affines.  The inputs are seeded, so two builds run with the same arguments can be compared file by file."""
+    import numpy as np  # noqa: PLC0415
+
+    os.makedirs(directory, exist_ok=True)
+    image = out["t1"]
+    data = image.data.detach()
+    arrays = {}
+    if data.numel() * 4 <= budget_bytes:
+        arrays["t1"] = data.float().cpu().numpy()
+    else:
+        flat = data.reshape(data.shape[0], -1)
+        per_volume = min(flat.shape[1], budget_bytes // 4 // flat.shape[0])
+        index = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(flat.shape[1], per_volume, replace=False))
+        arrays["t1"] = flat[:, torch.from_numpy(index).to(flat.device)].float().cpu().numpy()
+    arrays["t1_affine"] = torch.stack([affine.data.double().cpu() for affine in image.affines]).numpy()
+    written = {}
+    for name, array in arrays.items():
+        np.save(os.path.join(directory, f"{name}{suffix}.npy"), array)
+        written[f"{name}{suffix}"] = list(array.shape)
+    return written
+
+
 def time_mode(transform, batch, steps: int, *, noise_rng: str, precision: str, seed: int, timer=None, launch_bytes: int = 0, draw_policy: str | None = None,
               noise_plan: str | None = None) -> dict:
     """A few steps of the same Compose in another (noise rng, resample precision) mode: volumes/s on this GPU, and the
@@ -393,15 +428,21 @@ def main() -> None:
     parser.add_argument("--resample-precision", choices=["exact", "tight"], default="tight",
                         help="tight (default here, like --noise-rng philox: the throughput mode) = the reference's coordinates, taps and fill "
                              "decisions bit for bit, fused interpolation: inside the north-star bar PER VOXEL; exact = the library default, the "
-                             "reference's float32 operation sequence bit for bit.  The other modes are timed as well (mode_matrix) unless "
-                             "--no-mode-matrix")
+                             "reference's float32 operation sequence bit for bit.  With --full the other modes are timed as well (mode_matrix) "
+                             "unless --no-mode-matrix")
     parser.add_argument("--prewarm", type=int, default=100, help="untimed process pre-warm calls before the W warm-up steps")
     parser.add_argument("--settle-seconds", type=float, default=8.0, help="upper bound of the untimed settling phase after the pre-warm")
     parser.add_argument("--no-cpu-baseline", action="store_true")
     parser.add_argument("--cpu-volumes", type=int, default=8)
-    parser.add_argument("--no-aten-baseline", action="store_true", help="skip the stock-ATen restatement of the pipeline (the honest 'before')")
-    parser.add_argument("--no-other-configs", action="store_true", help="skip the fused tio.Spatial and config-5 (512^3 subject) legs (rank 0, N=1 only)")
-    parser.add_argument("--no-mode-matrix", action="store_true", help="skip the extra noise-rng / resample-precision legs (rank 0, N=1 only)")
+    parser.add_argument("--no-aten-baseline", action="store_true", help="--full: skip the stock-ATen restatement of the pipeline (the honest 'before')")
+    parser.add_argument("--no-other-configs", action="store_true", help="--full: skip the fused tio.Spatial and config-5 (512^3 subject) legs (rank 0, N=1 only)")
+    parser.add_argument("--no-mode-matrix", action="store_true", help="--full: skip the extra noise-rng / resample-precision legs (rank 0, N=1 only)")
+    parser.add_argument("--full", action="store_true",
+                        help="besides the headline: the roofline (HIP events around every resample launch of the timed steps), and with "
+                             "N=1 the mode matrix, multi-stream, the other configurations, the stock-ATen and CPU baselines and the "
+                             "measured HBM ceiling (each of those can still be left out with its --no-* switch)")
+    parser.add_argument("--dump-outputs", metavar="DIR", default=None,
+                        help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32 / float64)")
     args = parser.parse_args()
 
     info = tdist.init_process_group()
@@ -416,7 +457,7 @@ def main() -> None:
     tio.set_resample_precision(args.resample_precision)
     tio.set_stencil_precision(stencil_mode(args.resample_precision))  # the Blur's taps: fused multiply-adds in the throughput modes
     engine = ops.engine()
-    timer = KernelTimer(engine, "resample3d")
+    timer = KernelTimer(engine, "resample3d") if args.full else None  # (events inside the timed steps: --full only)
     transform = build_transform()
     batch = make_batch(args.size, args.batch, 1234 + info.rank, device)
     torch.manual_seed(4321 + info.rank)
@@ -453,7 +494,8 @@ def main() -> None:
     torch.cuda.synchronize()
     tdist.barrier()
     torch.cuda.synchronize()
-    timer.active = True
+    if timer is not None:
+        timer.active = True
     start = time.perf_counter()
     for _ in range(args.steps):
         out = transform(batch)
@@ -462,7 +504,11 @@ def main() -> None:
     tdist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - start
-    timer.active = False
+    if timer is not None:
+        timer.active = False
+    if args.dump_outputs:
+        # (every rank writes its own files: the budget is shared, so N ranks stay within what one writes)
+        dump_outputs(out, args.dump_outputs, f"_rank{info.rank}" if info.world_size > 1 else "", DUMP_BUDGET_BYTES // info.world_size)
 
     volume_bytes = args.size**3 * 4
     n_volumes = args.steps * args.batch
@@ -470,7 +516,7 @@ def main() -> None:
     total = tdist.aggregate_throughput(counters)
 
     if info.rank == 0:
-        kernel_ms = timer.mean_ms()
+        kernel_ms = timer.mean_ms() if timer is not None else None
         launch_bytes = 2 * volume_bytes * args.batch  # read input once + write output once, per launch
         achieved = launch_bytes / (kernel_ms * 1e-3) / 1e9 if kernel_ms else None
         precision = args.resample_precision
@@ -493,11 +539,11 @@ def main() -> None:
             "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
             "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
             "traffic": load_pmc(f"hbm_bytes_per_launch_{precision}"),
-            "launch_ms": kernel_ms, "algorithmic_bytes_per_launch": launch_bytes, "launches_timed": len(timer.pairs),
+            "launch_ms": kernel_ms, "algorithmic_bytes_per_launch": launch_bytes, "launches_timed": len(timer.pairs) if timer is not None else 0,
             "valu": valu,
         }
         extras: dict = {}
-        single = args.gpus == 1
+        single = args.gpus == 1 and args.full  # (the legs beyond the headline, rank 0 of one GPU: --full only)
         if single and not args.no_mode_matrix:
             # The headline value is the mode named in config.  The other modes of the same pipeline:
             #   noise "reference" = the reference's own stream, bit for bit (the library's default); "philox" = in-kernel draws;
@@ -587,8 +633,9 @@ def main() -> None:
             },
             "value_reference_identical": extras.get("value_reference_identical"),
             "host_enqueue_ms_per_step": 1e3 * host_enqueue_s / args.steps,
-            "roofline": roofline,
         }
+        if args.full:
+            line["roofline"] = roofline
         other = extras.get("other_configs")
         if other and other.get(f"fused_spatial,{precision}", {}).get("launch_ms"):
             fused_row = other[f"fused_spatial,{precision}"]

@@ -6,6 +6,7 @@
 set -u
 mkdir -p gpurun_out
 NATIVE=tests/native/_build
+OUT=${OUT_DIR:-validation_out}; mkdir -p "$OUT"  # (the bench lines of the steps bench / bench_quick)
 for step in "$@"; do
   case "$step" in
     tests)
@@ -29,9 +30,9 @@ for step in "$@"; do
     perf_exact)
       (cd $NATIVE && timeout 300 ./resample_bench --cases perf --case "f32" --reps 20 2>&1 | grep " ms " | cut -c1-130) | tee gpurun_out/r4_perf_all.log ;;
     bench)
-      timeout 600 python bench.py > gpurun_out/r4_bench.json 2> gpurun_out/r4_bench.err; tail -c 1500 gpurun_out/r4_bench.json; tail -3 gpurun_out/r4_bench.err ;;
+      timeout 600 python bench.py --full > $OUT/r4_bench.json 2> $OUT/r4_bench.err; tail -c 1500 $OUT/r4_bench.json; tail -3 $OUT/r4_bench.err ;;
     bench_quick)
-      timeout 300 python bench.py --no-cpu-baseline --no-aten-baseline --no-other-configs > gpurun_out/r4_bench_quick.json 2> gpurun_out/r4_bench_quick.err; tail -c 1200 gpurun_out/r4_bench_quick.json ;;
+      timeout 300 python bench.py --full --no-cpu-baseline --no-aten-baseline --no-other-configs > $OUT/r4_bench_quick.json 2> $OUT/r4_bench_quick.err; tail -c 1200 $OUT/r4_bench_quick.json ;;
     stencil)
       timeout 200 python scripts/bench_blur_stages.py 2>&1 | tail -20 | tee gpurun_out/r4_stencil.log ;;
     prof)
@@ -71,7 +72,7 @@ for step in "$@"; do
       L=gpurun_out/r4_ab_ahead.log; : > $L
       for rep in 1 2 3; do
         for off in 0 3 1 2; do
-          TIO_NO_AHEAD_STREAM=$((off & 1)) TIO_NO_ANNOUNCED_MIN=$((off >> 1)) timeout 200 python bench.py --steps 60 --no-cpu-baseline --no-aten-baseline --no-other-configs --no-mode-matrix 2>/dev/null |
+          TIO_NO_AHEAD_STREAM=$((off & 1)) TIO_NO_ANNOUNCED_MIN=$((off >> 1)) timeout 200 python bench.py --full --steps 60 --no-cpu-baseline --no-aten-baseline --no-other-configs --no-mode-matrix 2>/dev/null |
             python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('off(1=stream,2=announced min)=$off', round(d['value'],1), 'vol/s', round(d['ms_per_step'],4), 'ms/step host', round(d['host_enqueue_ms_per_step'],3), 'launch_ms', round(d['roofline']['launch_ms'],4))" >> $L
         done
       done

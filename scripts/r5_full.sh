@@ -5,10 +5,11 @@ timeout 90 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
 timeout 900 python -m pytest tests -m gpu -q --maxfail=10 > gpurun_out/r5_gpu_tests_full.txt 2>&1; tail -3 gpurun_out/r5_gpu_tests_full.txt; grep -E "^(FAILED|ERROR)" gpurun_out/r5_gpu_tests_full.txt | head
 (timeout 300 tests/native/_build/resample_bench --cases parity > gpurun_out/r5_native_parity_full.txt 2>&1; tail -1 gpurun_out/r5_native_parity_full.txt)
 (timeout 300 tests/native/_build/resample_bench --cases perf --reps 20 > gpurun_out/r5_native_perf_full.txt 2>&1; grep -c "ms " gpurun_out/r5_native_perf_full.txt)
-timeout 600 python bench.py > gpurun_out/r5_bench_full.json 2> gpurun_out/r5_bench_full.err; echo "bench rc $?"
-python - <<'PY'
-import json
-d=json.loads(open('gpurun_out/r5_bench_full.json').read().strip().splitlines()[-1])
+OUT=${OUT_DIR:-validation_out}; mkdir -p "$OUT"  # (the --full line: every leg the summary below reads)
+timeout 600 python bench.py --full > "$OUT/r5_bench_full.json" 2> "$OUT/r5_bench_full.err"; echo "bench rc $?"
+OUT="$OUT" python - <<'PY'
+import json, os
+d=json.loads(open(os.path.join(os.environ['OUT'], 'r5_bench_full.json')).read().strip().splitlines()[-1])
 print('value',round(d['value']),'ms',round(d['ms_per_step'],3),'host',round(d['host_enqueue_ms_per_step'],3),'roof',round(d['roofline']['frac'],3),round(d['roofline']['launch_ms'],3), 'traffic', d['roofline']['traffic'])
 for k,v in d['mode_matrix'].items(): print(' ',k, round(v['volumes_per_s']), round(v['ms_per_step'],3), round(v.get('resample_launch_ms',0),3))
 print(d.get('draw_policy')); print('ref identical', d.get('value_reference_identical'))

@@ -1,5 +1,5 @@
 #!/bin/bash
-# round 6, final tree: what the bench line's `roofline` is checked against —
+# round 6, final tree: what the `roofline` of the bench line (`bench.py --full`) is checked against —
 #   (1) rocprofv3 --kernel-trace --stats of the headline bench command and of a config-5 call,
 #   (2) SQ instruction counters of the exact-coordinate kernel (tight), affine and elastic launch: vector instructions per voxel,
 #   (3) HBM traffic of the same launches from the TCC counters (separate --pmc passes, kernel trace only; calibrated).

@@ -4,16 +4,20 @@ the image data (reference tests/test_noise.py:75-80, docs/concepts/transforms.md
 * the adjoint launch (``TIO_LINEAR_ADJOINT``) IS the transpose of the forward trilinear resampling: dot-product test
   <A x, g> == <x, A^T g> on random data, with and without elastic field / fill value;
 * the transforms backpropagate: Affine, ElasticDeformation, BiasField, Blur, Noise (Gaussian and Rician), Gamma, Flip;
-* build container: gradients equal the ones autograd derives through the UNMODIFIED reference.
+* gradients equal the ones autograd derived through the UNMODIFIED reference (recorded: tests/golden/reference_recorded.pt).
 CPU tests run the oracle; the ``gpu`` test repeats the adjoint and a Compose on the HIP engine.
 """
 from __future__ import annotations
+
+import os
 
 import pytest
 import torch
 
 import torchio_amd as tio
 from parity_harness import use_engine
+
+RECORDED = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_recorded.pt")
 
 
 def _geometry(device, elastic: bool):
@@ -138,30 +142,28 @@ def test_each_intensity_backward_against_finite_differences(oracle, name):
         assert abs(numeric - float(leaf.grad[index])) <= 2e-2 * max(1.0, abs(numeric)), (name, index, numeric, float(leaf.grad[index]))
 
 
-@pytest.mark.reference
-def test_gradients_equal_the_references_autograd(oracle):
-    import ref_import
-
-    if not ref_import.reference_available():
-        pytest.skip("/root/reference is only present in the build container")
-    theirs = ref_import.import_reference()
-
-    def grad_of(module, engine):
-        data = (torch.rand(1, 16, 14, 18, generator=torch.Generator().manual_seed(2)) + 0.2).requires_grad_(True)
-        pipe = module.Compose([
-            module.Affine(degrees=(-10, 10), scales=(0.9, 1.1), translation=(-2, 2)), module.ElasticDeformation(), module.BiasField(),
-            module.Blur(std=(0.5, 1.5)), module.Noise(std=0.1), module.Gamma(log_gamma=(-0.3, 0.3)),
-        ])
-        torch.manual_seed(9)
-        if engine is None:
+def reference_pipeline_grad(module, engine):
+    """The gradient of sum(out^2) through a six-transform Compose of *module* (*engine* None: the module's own code, as for
+    the reference; tests/golden/make_golden_reference.py records the reference's)."""
+    data = (torch.rand(1, 16, 14, 18, generator=torch.Generator().manual_seed(2)) + 0.2).requires_grad_(True)
+    pipe = module.Compose([
+        module.Affine(degrees=(-10, 10), scales=(0.9, 1.1), translation=(-2, 2)), module.ElasticDeformation(), module.BiasField(),
+        module.Blur(std=(0.5, 1.5)), module.Noise(std=0.1), module.Gamma(log_gamma=(-0.3, 0.3)),
+    ])
+    torch.manual_seed(9)
+    if engine is None:
+        out = pipe(module.Subject(t1=module.ScalarImage(data)))
+    else:
+        with use_engine(engine):
             out = pipe(module.Subject(t1=module.ScalarImage(data)))
-        else:
-            with use_engine(engine):
-                out = pipe(module.Subject(t1=module.ScalarImage(data)))
-        (out["t1"].data ** 2).sum().backward()
-        return data.grad
+    (out["t1"].data ** 2).sum().backward()
+    return data.grad
 
-    expected, actual = grad_of(theirs, None), grad_of(tio, oracle)
+
+def test_gradients_equal_the_references_autograd(oracle):
+    expected = torch.load(RECORDED, weights_only=True)["autograd"]["grad"]  # what autograd derived through the reference
+    actual = reference_pipeline_grad(tio, oracle)
+    assert actual.shape == expected.shape and actual.dtype == expected.dtype
     scale = expected.abs().max().item()
     assert (expected - actual).abs().max().item() <= 1e-4 * scale
 
