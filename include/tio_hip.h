@@ -183,7 +183,12 @@ typedef struct tio_resample_geom {
    * images — and that kernel plus the gap behind it sit on the critical path of the call (~8 - 23 us + ~5 us on the
    * bench launch).  A caller that knows the geometry before the data is ready (a Compose that has drawn every child's
    * parameters) can have the plan made on another stream while earlier work runs.  The plan must stay untouched until
-   * the call's kernels have finished; a call that takes another road than the one the plan was made for ignores it. */
+   * the call's kernels have finished; a call that takes another road than the one the plan was made for ignores it.
+   * A plan is valid for any number of tio_resample3d calls, one after the other on streams ordered behind each other,
+   * whose tio_resample_geom equals the one it was planned with (but for plan_dev / plan_bytes) — `flags` and `precision`
+   * included: the library checks only its size, and a plan made under another hint or precision can have the same size
+   * and drop bricks.
+   * (torchio_amd: Engine.resample_plan tags the plan with that signature, Engine.resample3d hands over only a match.) */
   const void* plan_dev;
   int64_t plan_bytes;
   /* TIO_GEOM_* bits (ABI 14; 0 = none).  Hints of a caller who holds the mappings on the host, about SPEED only: every road

@@ -990,3 +990,52 @@ def test_large_box_hint_reaches_the_geometry_struct():
         engine.resample3d([data], out_shape=(4, 4, 4), mapping=mapping, control_points=None, in_spacing=(1, 1, 1), out_spacing=(1, 1, 1),
                           affine_first=True, interps=["linear"], fills=[None], large_boxes=hint)
     assert [flags for name, flags in seen if name == "resample3d"] == [0, _abi.GEOM_LARGE_BOXES]
+
+
+def test_a_brick_plan_reaches_only_the_calls_it_was_made_for():
+    """ops.Engine: a plan made by `resample_plan` under one hint level and precision reaches tio_resample_geom.plan_dev of a call
+    made for the same (as its pointer), and of no other (NULL: that call plans for itself) — the library checks only a plan's
+    size, and a level-1 / level-2 plan has the size of the other level's and of a FAST / level-0 call's of fewer bytes."""
+    from torchio_amd import ops
+
+    handed = []
+
+    class Fake(dict):
+        def __missing__(self, key):
+            def call(*args):
+                if key == "resample3d_plan_bytes":
+                    return 256
+                if key == "resample3d":
+                    handed.append(args[0]._obj.plan_dev)
+                return 0
+
+            return call
+
+        def __contains__(self, key):
+            return key != "last_error"
+
+    engine = ops.Engine(Fake(), "cpu", "fake")
+    data = torch.zeros(1, 1, 4, 4, 4)
+    geometry = dict(out_shape=(4, 4, 4), mapping=torch.eye(4)[:3].unsqueeze(0), control_points=None, in_spacing=(1, 1, 1),
+                    out_spacing=(1, 1, 1), affine_first=True)
+
+    def call(plan, **changes):
+        handed.clear()
+        engine.resample3d([data], interps=["linear"], fills=[None], plan=plan, **{**geometry, **changes})
+        return handed[0]
+
+    cells = [(level, precision) for level in (0, 1, 2) for precision in ("fast", "tight", "exact")]
+    for made_for in cells:
+        plan = engine.resample_plan(batch=1, in_shape=(4, 4, 4), precision=made_for[1], large_boxes=made_for[0], **geometry)
+        assert plan is not None
+        for level, precision in cells:
+            expected = plan.data_ptr() if (level, precision) == made_for else None
+            assert call(plan, precision=precision, large_boxes=level) == expected, (made_for, level, precision)
+    # ... the rest of what the plan was made for: control points or not, composition order, output shape; and a tensor that
+    # `resample_plan` did not make (a slice of a plan) is not a plan
+    plan = engine.resample_plan(batch=1, in_shape=(4, 4, 4), precision="exact", **geometry)
+    assert call(plan, precision="exact") == plan.data_ptr()
+    assert call(plan, precision="exact", control_points=torch.zeros(1, 7, 7, 7, 3)) is None
+    assert call(plan, precision="exact", affine_first=False) is None
+    assert call(plan, precision="exact", out_shape=(4, 4, 8)) is None
+    assert call(plan[:32], precision="exact") is None

@@ -1057,7 +1057,8 @@ static int resample3d_impl(const tio_resample_geom* geom, int32_t n_images, cons
           const int plan_threads = n_items * plan_lanes > a.B ? n_items * plan_lanes : a.B;
           const dim3 plan_grid((plan_threads + 255) / 256);
           // the header of the multi-pass bricks' list (length, cursor, done count) is zero between launches: the leased workspace is
-          // zeroed when it is allocated and the last walker of a launch leaves zeros; a caller's buffer is zeroed here
+          // zeroed when it is allocated and the last walker of a call's last launch leaves zeros; a caller's buffer is zeroed here —
+          // and keeps its length after every call it is handed to (la.last_use below: a plan made ahead serves any number of calls)
           if (a.plan_multi && mode == kPlanOnly && hipMemsetAsync(plan - kPlanHeaderInts, 0, kPlanHeaderInts * sizeof(int), s) != hipSuccess)
             return fail(TIO_ERR_LAUNCH, "tio_resample3d_plan: cannot reset the brick plan");
           if (a.cp != nullptr) hipLaunchKernelGGL((plan_bricks_kernel<true, 16, 16, 16>), plan_grid, dim3(256), 0, s, a, plan, n_items);
@@ -1189,7 +1190,7 @@ static int resample3d_impl(const tio_resample_geom* geom, int32_t n_images, cons
                   have_first = true;
                   continue;
                 }
-                la.last_use = launches_left == 0;
+                la.last_use = !planned_ahead && launches_left == 0;
                 la.min_keys = nullptr;
                 const bool with_label = label_here && launches_left == 0;
                 if (have_first) {
@@ -1217,7 +1218,7 @@ static int resample3d_impl(const tio_resample_geom* geom, int32_t n_images, cons
               la.out = static_cast<float*>(g.out) + static_cast<int64_t>(c) * n_out;
               la.fill = g.fill != nullptr ? g.fill + c : nullptr;
               la.min_keys = (min_channels > 0 && g.min_keys != nullptr) ? g.min_keys + c * kMinSlots : nullptr;
-              la.last_use = --launches_left == 0;
+              la.last_use = --launches_left == 0 && !planned_ahead;
               hipLaunchKernelGGL(kernel, dim3(grid_launch), dim3(block_launch), lds_launch, s, la);
               if (walk_list) hipLaunchKernelGGL(kernel_multi, dim3(grid_multi), dim3(block_launch), lds_launch, s, la);
             }

@@ -958,7 +958,9 @@ __global__ __launch_bounds__(256, 3) void resample_lean_exact_all_kernel(const L
 // holds the 1.6 % of the bricks that sampled voxel by voxel from global memory until round 5 — every walker takes one or
 // none; beyond ~12 degrees about all axes it holds most bricks.  The last walker to finish zeroes cursor and done count — and
 // the list's length when the host says this launch is the last one that reads this plan (a.last_use: the launches of a call's
-// channels share a plan) — so the planner starts from zeros without a memset on the stream.
+// channels share a plan) — so the planner starts from zeros without a memset on the stream.  a.last_use is set only on the
+// call's own leased plan: a plan made ahead (tio_resample3d_plan, zeroed before its planner runs) serves any number of calls,
+// each of which must find its list's length where the planner left it.
 // (Both kinds of blocks in ONE launch — walkers behind the bricks' own blocks — were built and measured: +9 % on the bench's
 // affine launch, the register allocation of the walker's body leaks into the one-brick body; profiles/r06_resample.md.)
 template <bool ELASTIC_POSSIBLE, bool EXACT_LERP, bool FOLD_MIN = false>

@@ -949,6 +949,13 @@ class Engine:
         self._check("resample3d", mapping, control_points, cp_skip, passthrough)
         return geom, [mapping, control_points, cp_skip, passthrough]
 
+    @staticmethod
+    def _plan_signature(geom) -> tuple:
+        """What a brick plan is made for (include/tio_hip.h: plan_dev): the road and the plan's layout follow from these fields
+        — the C side checks only a plan's size, and a plan made under another hint or precision can have the size of the call's."""
+        return (geom.precision, geom.flags, geom.batch, tuple(geom.in_shape), tuple(geom.out_shape), geom.control_points_dev is not None,
+                geom.affine_first)
+
     def resample_plan(
         self, *, batch: int, in_shape, out_shape, mapping: Tensor, control_points: Tensor | None, in_spacing, out_spacing,
         affine_first: bool, cp_skip: Tensor | None = None, passthrough: Tensor | None = None, norm_shape=None,
@@ -957,15 +964,17 @@ class Engine:
         """The brick plan of the launch ``resample3d`` would make for this geometry with float32 trilinear images, enqueued on
         the CURRENT stream of the mapping's device (``tio_resample3d_plan``, ABI 11) — or ``None`` when that launch takes a
         road without a plan (small batches, ...).  Hand the tensor to ``resample3d(..., plan=...)`` with the same geometry, on
-        a stream ordered behind this one; the planning kernel then leaves that call's critical path."""
-        if "resample3d_plan" not in self._fn or mapping.device.type != "cuda":
+        a stream ordered behind this one; the planning kernel then leaves that call's critical path.  The plan serves any number
+        of such calls; it carries what it was made for (precision, hint, batch, shapes, control points or not, composition
+        order), and a call made for something else ignores it."""
+        if "resample3d_plan" not in self._fn or mapping.device.type != self.device_type:
             return None
         geom, keep_alive = self._resample_geom(
             batch, tuple(in_shape), tuple(int(s) for s in out_shape), mapping, control_points, in_spacing, out_spacing,
             affine_first, cp_skip, passthrough, norm_shape, precision, large_boxes,
         )
         reference = keep_alive[0]
-        if reference.device.index != torch.cuda.current_device():
+        if self.device_type == "cuda" and reference.device.index != torch.cuda.current_device():
             with torch.cuda.device(reference.device):
                 size = self._fn["resample3d_plan_bytes"](C.byref(geom))
         else:
@@ -974,6 +983,7 @@ class Engine:
             return None
         plan = torch.empty((size + 3) // 4, dtype=torch.int32, device=reference.device)
         self._call("resample3d_plan", reference, C.byref(geom), C.c_void_p(plan.data_ptr()), size, self._stream(reference))
+        plan._tio_plan_signature = self._plan_signature(geom)  # (`resample3d` hands the plan only to calls of this signature)
         del keep_alive
         return plan
 
@@ -1027,7 +1037,9 @@ class Engine:
             norm_shape, precision, large_boxes,
         )
         mapping, control_points, cp_skip, passthrough = keep_alive[:4]
-        if plan is not None and plan.device == first.device:  # made ahead by `resample_plan` for exactly this geometry
+        # made ahead by `resample_plan` for this geometry: a plan made under another hint or precision — or not by
+        # `resample_plan` — stays with its maker (the call plans for itself)
+        if plan is not None and plan.device == first.device and getattr(plan, "_tio_plan_signature", None) == self._plan_signature(geom):
             geom.plan_dev = plan.data_ptr()
             geom.plan_bytes = plan.numel() * plan.element_size()
             keep_alive.append(plan)
