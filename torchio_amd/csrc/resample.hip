@@ -18,7 +18,10 @@
 // "interior" path (all 8 taps of all 64 lanes in bounds: no predication, no
 // mask arithmetic — the mask is exactly > 0.5 there), (3) IEEE-exact division
 // by reciprocal + two FMA refinements instead of the 12-instruction expansion.
-#include <functional>
+//
+// Host side, at the end of this file: the dispatcher — check_geometry, sort_images, choose_float_road (which road a call takes and why; the table
+// is in DESIGN.md 4.1) and one launcher per road, tied together by resample3d_impl.
+#include <type_traits>
 #include <stdlib.h>
 #include <string.h>
 
@@ -664,25 +667,131 @@ static PlanLease plan_workspace(hipStream_t s, size_t bytes) {
   return lease;
 }
 
-// `folded` comes back true when the launch itself produced every requested out_min_dev (planned FAST bricks)
-// `mode`: kPlanNone — the call itself; kPlanQuery — only *plan_bytes (the plan this geometry's launch would start from; 0: none);
-// kPlanOnly — enqueue the planning kernel into plan_out and return (tio_resample3d_plan).  The two plan modes run the same
-// decisions as the call, with one float32 trilinear image standing in for the caller's (the planner never reads an image).
-enum { kPlanNone = 0, kPlanQuery = 1, kPlanOnly = 2 };
-static int resample3d_impl(const tio_resample_geom* geom, int32_t n_images, const tio_resample_image* images, void* stream, bool* folded,
-                           int mode = kPlanNone, int* plan_out = nullptr, int64_t plan_out_bytes = 0, int64_t* plan_bytes = nullptr) {
-  using namespace tio;
-  *folded = false;
-  if (plan_bytes != nullptr) *plan_bytes = 0;
-  tio_resample_image stand_in{};
-  if (mode != kPlanNone) {
-    static float aligned_dummy[4] __attribute__((aligned(16)));  // never dereferenced: the plan modes return before any sampling launch
-    stand_in.in = aligned_dummy; stand_in.out = aligned_dummy; stand_in.channels = 1; stand_in.dtype = TIO_F32; stand_in.interp = TIO_LINEAR;
-    images = &stand_in; n_images = 1;
+// The dispatcher of tio_resample3d.  resample3d_impl (at the end) reads top to bottom: check_geometry, sort_images, the side groups (launch_nearest, launch_label_pv,
+// launch_bspline), choose_float_road, that road's launcher.  choose_float_road makes no HIP call and is the only place where a switch or a threshold decides the float
+// group's road; tio_resample3d_plan_bytes / tio_resample3d_plan ask it the same question for one aligned float32 image.
+namespace {
+using namespace tio;
+
+// run-time booleans -> template arguments: f is called with one std::bool_constant per flag, in the order given
+// (every combination of the flags is instantiated: pass only flags whose whole cross product exists)
+template <typename F>
+auto with_bools(F f) { return f(); }
+template <typename F, typename... Rest>
+auto with_bools(F f, bool first, Rest... rest) {
+  return first ? with_bools([&](auto... c) { return f(std::true_type{}, c...); }, rest...)
+               : with_bools([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
+}
+// ... and an element size of 1, 2, 4 or 8 bytes
+template <typename F>
+void with_element_size(int es, F f) {
+  if (es == 1) f(std::integral_constant<int, 1>{});
+  else if (es == 2) f(std::integral_constant<int, 2>{});
+  else if (es == 4) f(std::integral_constant<int, 4>{});
+  else f(std::integral_constant<int, 8>{});
+}
+
+using RowsKernel = void (*)(ResampleArgs);               // resample_kernel
+using BrickKernel = void (*)(ResampleArgs, const int*);  // resample_tile_kernel, resample_planned_kernel
+using LeanKernel = void (*)(LeanArgs);                   // resample_planned_lean_kernel, resample_lean_exact_*_kernel
+
+// multiply-high reciprocal of a divisor (0: the divisor is 1, nothing to divide)
+unsigned magic_u32(unsigned n) { return n > 1 ? 0xFFFFFFFFu / n + 1u : 0u; }
+
+// tiles of ti x tj x tk output voxels: their counts per axis, the reciprocals, and one block per tile of every batch element
+template <typename Args>
+int set_tiles(Args& a, int ti, int tj, int tk, unsigned* blocks) {
+  a.tiles_k = (a.Ko + tk - 1) / tk; a.tiles_j = (a.Jo + tj - 1) / tj; a.tiles_i = (a.Io + ti - 1) / ti;
+  a.magic_k = magic_u32(a.tiles_k); a.magic_j = magic_u32(a.tiles_j); a.magic_i = magic_u32(a.tiles_i);
+  const int64_t n = static_cast<int64_t>(a.B) * a.tiles_i * a.tiles_j * a.tiles_k;
+  if (n >= (1LL << 31)) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_resample3d: grid too large");
+  *blocks = static_cast<unsigned>(n);
+  return TIO_OK;
+}
+
+// more than 48 KiB of dynamic LDS have to be asked for, kernel by kernel
+template <typename Kernel>
+int reserve_lds(Kernel kernel, size_t bytes) {
+  if (bytes > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes)) != hipSuccess)
+    return fail(TIO_ERR_LAUNCH, "tio_resample3d: cannot reserve %zu bytes of LDS", bytes);
+  return TIO_OK;
+}
+
+int control_floats(const ResampleArgs& a) { return a.cp != nullptr ? a.ni * a.nj * a.nk * 3 : 0; }
+bool control_points_fit_lds(const ResampleArgs& a) { return control_floats(a) > 0 && control_floats(a) <= kMaxCpLds; }
+
+// Where a planned road's plan lives: a plan made ahead by tio_resample3d_plan (geom->plan_dev: no planning kernel on this stream) or the stream's leased workspace.  The
+// lease is held as long as this object lives: the launcher keeps it until the last kernel that reads the plan is enqueued.
+struct Plan {
+  PlanLease lease;
+  int* ptr = nullptr;  // behind the header
+  bool made_ahead = false;
+};
+int acquire_plan(const tio_resample_geom* geom, size_t need, hipStream_t s, Plan* plan) {
+  if (geom->plan_dev != nullptr && geom->plan_bytes >= static_cast<int64_t>(need) && (reinterpret_cast<uintptr_t>(geom->plan_dev) & 15) == 0) {
+    plan->ptr = static_cast<int*>(const_cast<void*>(geom->plan_dev)) + kPlanHeaderInts;
+    plan->made_ahead = true;
+    return TIO_OK;
   }
-  if (geom == nullptr || images == nullptr) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_resample3d: null argument");
-  if (n_images < 1 || n_images > TIO_MAX_IMAGES)
-    return fail(TIO_ERR_INVALID_ARGUMENT, "tio_resample3d: n_images=%d not in [1, %d]", n_images, TIO_MAX_IMAGES);
+  plan->lease = plan_workspace(s, need);
+  if (plan->lease.ptr == nullptr) return fail(TIO_ERR_LAUNCH, "tio_resample3d: cannot allocate the brick plan");
+  plan->ptr = plan->lease.ptr + kPlanHeaderInts;
+  return TIO_OK;
+}
+
+// plan_bricks_kernel for the 16^3 bricks of `a` (set_tiles and apply_road have run): plan_group lanes per brick
+void enqueue_planner(const ResampleArgs& a, int* plan, int n_items, hipStream_t s) {
+  const int plan_lanes = plan_group(a.cp != nullptr);
+  const int plan_threads = n_items * plan_lanes > a.B ? n_items * plan_lanes : a.B;
+  const dim3 plan_grid((plan_threads + 255) / 256);
+  with_bools([&](auto elastic) { hipLaunchKernelGGL((plan_bricks_kernel<elastic.value, 16, 16, 16>), plan_grid, dim3(256), 0, s, a, plan, n_items); }, a.cp != nullptr);
+}
+
+// the 16^3 bricks of a planned road and their plan: the planner is enqueued unless the plan was made ahead
+int plan_bricks(const tio_resample_geom* geom, ResampleArgs& a, size_t plan_need, hipStream_t s, Plan* plan, int* n_items) {
+  unsigned bricks = 0;
+  if (const int st = set_tiles(a, 16, 16, 16, &bricks)) return st;
+  *n_items = static_cast<int>(bricks);  // (choose_float_road: below 2^26)
+  if (const int st = acquire_plan(geom, plan_need, s, plan)) return st;
+  if (!plan->made_ahead) enqueue_planner(a, plan->ptr, *n_items, s);
+  return TIO_OK;
+}
+
+// The folded minimum of the planned FAST / lean roads: kMinSlots keys per channel that asked for it (common.hpp: min_workspace, all ones between launches; its own array,
+// kind 1: tio_channel_min may be enqueued between a launch's kernels), finished by min_finish_kernel behind the sampling kernels.  Taken while the plan lease is held.
+// channels == 0: nothing folds, and the images' out_min are cleared (tio_resample3d then runs the plain reduction).
+struct FoldedMin {
+  uint32_t* keys = nullptr;
+  MinOuts outs{};
+  int channels = 0;
+};
+int take_folded_min(ResampleArgs& a, bool allowed, hipStream_t s, FoldedMin* m) {
+  for (int i = 0; i < a.n_images; i++) m->channels += a.img[i].out_min != nullptr ? a.img[i].channels : 0;
+  if (m->channels == 0 || m->channels > kMinChannels || !allowed) {
+    m->channels = 0;
+    for (int i = 0; i < a.n_images; i++) a.img[i].out_min = nullptr;
+    return TIO_OK;
+  }
+  int cap = 0;
+  m->keys = min_workspace(s, m->channels * kMinSlots, &cap, /*kind=*/1);
+  if (m->keys == nullptr) return fail(TIO_ERR_LAUNCH, "tio_resample3d: cannot allocate the reduction workspace");
+  int slot = 0;
+  for (int i = 0; i < a.n_images; i++)
+    if (a.img[i].out_min != nullptr) {
+      a.img[i].min_keys = m->keys + slot * kMinSlots;
+      for (int c = 0; c < a.img[i].channels; c++) m->outs.p[slot + c] = a.img[i].out_min + c;
+      slot += a.img[i].channels;
+    }
+  return TIO_OK;
+}
+
+void finish_folded_min(const FoldedMin& m, hipStream_t s) {
+  if (m.channels > 0)
+    hipLaunchKernelGGL(min_finish_kernel, dim3(static_cast<unsigned>(m.channels)), dim3(kMinSlots), 0, s, m.keys, m.outs, m.channels);
+}
+
+// fills the part of ResampleArgs that every group of images shares; an empty batch leaves a.B == 0 (nothing to do)
+int check_geometry(const tio_resample_geom* geom, ResampleArgs& a) {
   if (geom->batch < 0) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_resample3d: negative batch");
   if (geom->batch == 0) return TIO_OK;  // an empty batch has no data pointers to speak of
   if (geom->mapping_dev == nullptr) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_resample3d: mapping_dev is null");
@@ -701,7 +810,6 @@ static int resample3d_impl(const tio_resample_geom* geom, int32_t n_images, cons
       if (geom->cp_shape[d] < 1) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_resample3d: bad cp_shape");
   }
 
-  ResampleArgs a{};
   a.B = geom->batch;
   a.I = geom->in_shape[0]; a.J = geom->in_shape[1]; a.K = geom->in_shape[2];
   a.Io = geom->out_shape[0]; a.Jo = geom->out_shape[1]; a.Ko = geom->out_shape[2];
@@ -738,22 +846,35 @@ static int resample3d_impl(const tio_resample_geom* geom, int32_t n_images, cons
     a.scale_j = lerp_scale(a.nj, a.Jo);
     a.scale_k = lerp_scale(a.nk, a.Ko);
   }
-  // "label" partial-volume images go through their own launch of the gather kernel (same
-  // coordinates); everything else shares one launch of the brick / gather kernel
-  ResampleArgs pv = a;
-  ResampleArgs spl = a;  // B-spline images (TIO_QUADRATIC / TIO_CUBIC): their own launch of the gather kernel as well
-  // nearest images without a fill rule (label maps): their own kernel (resample_nearest.hpp), bit-identical to the exact
-  // chain whatever the precision mode of the call; TIO_NEAREST_KERNEL=0 keeps them with the other images (A/B)
+  return TIO_OK;
+}
+
+NearestArgs make_nearest_args(const ResampleArgs& a) {
   NearestArgs nn{};
-  const EnvSwitches& env = env_switches();  // (parsed once per process / tio_reload_env(): no getenv on this road)
-  const bool nn_enabled = env.nearest_kernel != 0 &&
-                          static_cast<int64_t>(a.I) * a.J <= (1LL << 24) && a.K < (1 << 24);
-  a.n_images = 0;
-  pv.n_images = 0;
-  pv.any_linear = 1;
-  spl.n_images = 0;
-  int dtmode = 0;
-  bool any_adjoint = false;
+  nn.B = a.B; nn.I = a.I; nn.J = a.J; nn.K = a.K; nn.Io = a.Io; nn.Jo = a.Jo; nn.Ko = a.Ko; nn.affine_first = a.affine_first;
+  nn.mapping = a.mapping; nn.cp = a.cp; nn.cp_skip = a.cp_skip; nn.passthrough = a.passthrough;
+  nn.mapping_batched = a.mapping_batched; nn.cp_batched = a.cp_batched; nn.ni = a.ni; nn.nj = a.nj; nn.nk = a.nk;
+  nn.unit_spacing = a.unit_spacing;
+  nn.scale_i = a.scale_i; nn.scale_j = a.scale_j; nn.scale_k = a.scale_k;
+  for (int d = 0; d < 3; d++) {
+    nn.sp[d] = a.sp[d]; nn.rsp[d] = a.rsp[d]; nn.den[d] = a.den[d]; nn.rden[d] = a.rden[d]; nn.size_m1[d] = a.size_m1[d];
+    nn.ratio[d] = a.half_h[d] / a.dh[d];
+    nn.dh[d] = a.dh[d]; nn.rdh[d] = a.rdh[d]; nn.half_h[d] = a.half_h[d];
+  }
+  return nn;
+}
+
+// what choose_float_road needs to know of the float group `a` beyond a.any_linear / a.any_nearest
+struct FloatGroup {
+  int dtmode = 0;            // 0: float32 images only, 1: small integers as well, 2: any dtype
+  bool any_adjoint = false;  // a TIO_LINEAR_ADJOINT image (scatters to global memory)
+  bool rows16 = true;        // every input starts on a 16-byte boundary
+};
+// a: everything that shares the brick / gather launch; pv: TIO_LABEL_PV images and spl: B-spline images (each their own launch of the gather kernel, same coordinates);
+// nn: nearest images (label maps) for their own kernel (resample_nearest.hpp: bit-identical to the exact chain in every precision mode; TIO_NEAREST_KERNEL=0: they stay in `a`)
+int sort_images(int32_t n_images, const tio_resample_image* images, const EnvSwitches& env, ResampleArgs& a, ResampleArgs& pv, ResampleArgs& spl, NearestArgs& nn,
+                FloatGroup& group) {
+  const bool nn_enabled = env.nearest_kernel != 0 && static_cast<int64_t>(a.I) * a.J <= (1LL << 24) && a.K < (1 << 24);
   for (int i = 0; i < n_images; i++) {
     const tio_resample_image& s = images[i];
     if (s.in == nullptr || s.out == nullptr || s.channels < 1)
@@ -770,7 +891,7 @@ static int resample3d_impl(const tio_resample_geom* geom, int32_t n_images, cons
     }
     if (s.interp == TIO_LINEAR_ADJOINT) {
       if (s.dtype != TIO_F32) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_resample3d: image %d: the adjoint works on float32 gradients", i);
-      any_adjoint = true;
+      group.any_adjoint = true;
     }
     if (s.interp == TIO_LABEL_PV) {
       if (s.channels != 1)
@@ -780,7 +901,7 @@ static int resample3d_impl(const tio_resample_geom* geom, int32_t n_images, cons
       pv.img[pv.n_images++] = ImgArgs{s.in, s.out, nullptr, 1, s.dtype, s.interp, s.labels_dev, s.n_labels, s.pad_label, nullptr, nullptr};
       continue;
     }
-    if (nn_enabled && s.interp == TIO_NEAREST && s.out_min_dev == nullptr) {  // (with or without a fill rule: round 4)
+    if (nn_enabled && s.interp == TIO_NEAREST && s.out_min_dev == nullptr) {  // (with or without a fill rule)
       nn.img[nn.n_images++] = NearestImg{s.in, s.out, s.channels, dtype_size(s.dtype), s.fill_dev, s.dtype};
       if (s.fill_dev != nullptr) nn.any_fill = 1;
       continue;
@@ -790,559 +911,437 @@ static int resample3d_impl(const tio_resample_geom* geom, int32_t n_images, cons
     if (s.interp == TIO_LINEAR || s.interp == TIO_LINEAR_ADJOINT || s.fill_dev != nullptr) a.any_linear = 1;
     if (s.interp == TIO_NEAREST) a.any_nearest = 1;
     const int need = s.dtype == TIO_F32 ? 0 : ((s.dtype == TIO_I16 || s.dtype == TIO_U8 || s.dtype == TIO_I32) ? 1 : 2);
-    dtmode = need > dtmode ? need : dtmode;
+    group.dtmode = need > group.dtmode ? need : group.dtmode;
+    group.rows16 = group.rows16 && (reinterpret_cast<uintptr_t>(s.in) & 15) == 0;
   }
-  if (a.B == 0) return TIO_OK;
+  return TIO_OK;
+}
 
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int n_cp = a.cp != nullptr ? a.ni * a.nj * a.nk * 3 : 0;
+// ---- the road of the float group: which one is taken when, and the kernels behind each, is the table of DESIGN.md 4.1 ----
+enum FloatRoadKind { kRoadGather, kRoadBrick, kRoadPlannedBrick, kRoadFastBrick, kRoadPlannedFast, kRoadPlannedLean, kRoadLeanExact };
 
-  // round 6: ONE plain label channel of a call that also samples float32 images may ride along the images' last exact-coordinate
-  // launch (resample_lean_exact_label_kernel) instead of taking its own kernel; whatever road the images take in the end — every
-  // return below — the label map is sampled: if nobody has taken it along, its own launch goes out when this scope is left
-  struct DeferredLaunch {
-    std::function<void()> launch;
-    ~DeferredLaunch() { if (launch) launch(); }
-  } label_rides;
-  int label_es = 0;
-  if (nn.n_images > 0) {
-    nn.B = a.B; nn.I = a.I; nn.J = a.J; nn.K = a.K; nn.Io = a.Io; nn.Jo = a.Jo; nn.Ko = a.Ko; nn.affine_first = a.affine_first;
-    nn.mapping = a.mapping; nn.cp = a.cp; nn.cp_skip = a.cp_skip; nn.passthrough = a.passthrough;
-    nn.mapping_batched = a.mapping_batched; nn.cp_batched = a.cp_batched; nn.ni = a.ni; nn.nj = a.nj; nn.nk = a.nk;
-    nn.unit_spacing = a.unit_spacing;
-    nn.scale_i = a.scale_i; nn.scale_j = a.scale_j; nn.scale_k = a.scale_k;
-    for (int d = 0; d < 3; d++) {
-      nn.sp[d] = a.sp[d]; nn.rsp[d] = a.rsp[d]; nn.den[d] = a.den[d]; nn.rden[d] = a.rden[d]; nn.size_m1[d] = a.size_m1[d];
-      nn.ratio[d] = a.half_h[d] / a.dh[d];
-      nn.dh[d] = a.dh[d]; nn.rdh[d] = a.rdh[d]; nn.half_h[d] = a.half_h[d];
-    }
-    const bool nn_rows = nn.Ko >= 48;  // bricks of 16 x 4 x 64 (a wave = one output row) unless the volume is narrower than that
-    const int nn_tj = nn_rows ? 4 : 16, nn_tk = nn_rows ? 64 : 16;
-    nn.tiles_k = (nn.Ko + nn_tk - 1) / nn_tk; nn.tiles_j = (nn.Jo + nn_tj - 1) / nn_tj; nn.tiles_i = (nn.Io + 15) / 16;
-    nn.magic_k = nn.tiles_k > 1 ? 0xFFFFFFFFu / nn.tiles_k + 1u : 0u;
-    nn.magic_j = nn.tiles_j > 1 ? 0xFFFFFFFFu / nn.tiles_j + 1u : 0u;
-    nn.magic_i = nn.tiles_i > 1 ? 0xFFFFFFFFu / nn.tiles_i + 1u : 0u;
-    const int64_t blocks = static_cast<int64_t>(nn.B) * nn.tiles_i * nn.tiles_j * nn.tiles_k;
-    if (blocks >= (1LL << 31)) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_resample3d: grid too large");
-    nn.eps = kNearestEps;
-    if (env.has_nearest_eps) nn.eps = env.nearest_eps;  // (calibration runs only)
-    const dim3 grid(static_cast<unsigned>(blocks)), block(256);
-    // round 6: without a fill rule the reference's own coordinates plane by plane (resample_nearest_exact_kernel; its gate is the
-    // float exact-coordinate kernel's: the short division, unit spacing under control points, rows of at least 48 voxels)
-    const bool nn_exact = env.nearest_exact != 0 && nn.any_fill == 0 && nn_rows && a.short_div != 0 && (a.cp == nullptr || a.unit_spacing != 0);
-    for (int es = 1; es <= 8; es *= 2) {  // one launch per element size present
-      bool present = false;
-      for (int i = 0; i < nn.n_images; i++) present = present || nn.img[i].es == es;
-      if (!present) continue;
-      // ... and its tail's: 24-bit offsets and buffer loads (I J <= 2^24, every channel below 2^32 bytes)
-      const int64_t n_in_e = static_cast<int64_t>(nn.I) * nn.J * nn.K, n_out_e = static_cast<int64_t>(nn.Io) * nn.Jo * nn.Ko;
-      const bool nn_narrow = static_cast<int64_t>(nn.I) * nn.J <= (1 << 24) && static_cast<int64_t>(nn.K) * es < (1 << 24) &&
-                             n_in_e * es < (int64_t{1} << 32) - 16 && n_out_e * es < (int64_t{1} << 32) - 16;
-      if (nn_exact && nn_narrow && env.lean_label != 0 && nn.n_images == 1 && nn.img[0].channels == 1 && es <= 4 && a.n_images > 0 && pv.n_images == 0 &&
-          spl.n_images == 0 && !any_adjoint) {
-        const unsigned nn_lds = env.nearest_lds >= 0 ? static_cast<unsigned>(env.nearest_lds) : (nn.cp == nullptr ? 52000u : 0u);
-        label_es = es;
-        label_rides.launch = [nn, grid, block, nn_lds, s, es]() {
-#define TIO_NN_EXACT(ES)                                                                                                \
-  if (nn.cp != nullptr) hipLaunchKernelGGL((resample_nearest_exact_kernel<true, ES>), grid, block, nn_lds, s, nn);           \
-  else hipLaunchKernelGGL((resample_nearest_exact_kernel<false, ES>), grid, block, nn_lds, s, nn);
-          if (es == 1) { TIO_NN_EXACT(1) } else if (es == 2) { TIO_NN_EXACT(2) } else { TIO_NN_EXACT(4) }
-#undef TIO_NN_EXACT
-        };
-        continue;
-      }
-      if (nn_exact && nn_narrow) {
-        // resident blocks per CU through UNUSED dynamic LDS: without control points the kernel holds 61 registers (eight blocks per CU),
-        // and eight blocks' slanted input footprints evict one another's cache lines — three blocks per CU measured 0.236 -> 0.210 ms
-        // (int16) and 0.344 -> 0.286 (int32) on 8 x 256^3 at the bench's ranges, uint8 0.172 -> 0.177; with control points (95 registers,
-        // five blocks) the launch is arithmetic bound and loses from four blocks down (profiles/r06_labels.md).  TIO_NEAREST_LDS: A/B
-        const unsigned nn_lds = env.nearest_lds >= 0 ? static_cast<unsigned>(env.nearest_lds) : (nn.cp == nullptr ? 52000u : 0u);
-#define TIO_NN_EXACT(ES)                                                                                                \
-  if (nn.cp != nullptr) hipLaunchKernelGGL((resample_nearest_exact_kernel<true, ES>), grid, block, nn_lds, s, nn);           \
-  else hipLaunchKernelGGL((resample_nearest_exact_kernel<false, ES>), grid, block, nn_lds, s, nn);
-        if (es == 1) { TIO_NN_EXACT(1) } else if (es == 2) { TIO_NN_EXACT(2) } else if (es == 4) { TIO_NN_EXACT(4) } else { TIO_NN_EXACT(8) }
-#undef TIO_NN_EXACT
-        continue;
-      }
-#define TIO_NN_LAUNCH_SHAPE(ES, TJ, TK)                                                                                 \
-  if (nn.cp != nullptr) hipLaunchKernelGGL((resample_nearest_kernel<true, ES, TJ, TK, 16>), grid, block, 0, s, nn);     \
-  else hipLaunchKernelGGL((resample_nearest_kernel<false, ES, TJ, TK, 16>), grid, block, 0, s, nn);
-#define TIO_NN_LAUNCH(ES)                                                                                               \
-  if (nn_rows) { TIO_NN_LAUNCH_SHAPE(ES, 4, 64) } else { TIO_NN_LAUNCH_SHAPE(ES, 16, 16) }
-      if (es == 1) { TIO_NN_LAUNCH(1) } else if (es == 2) { TIO_NN_LAUNCH(2) } else if (es == 4) { TIO_NN_LAUNCH(4) } else { TIO_NN_LAUNCH(8) }
-#undef TIO_NN_LAUNCH
-#undef TIO_NN_LAUNCH_SHAPE
-    }
-    if (a.n_images == 0 && pv.n_images == 0 && spl.n_images == 0) return check_launch("tio_resample3d");
-  }
-  if (pv.n_images > 0) {
-    pv.tiles_k = (pv.Ko + kLanes - 1) / kLanes;
-    pv.tiles_j = (pv.Jo + kRowsPerBlock - 1) / kRowsPerBlock;
-    pv.tiles_i = (pv.Io + kTileI - 1) / kTileI;
-    const int64_t blocks = static_cast<int64_t>(pv.B) * pv.tiles_i * pv.tiles_j * pv.tiles_k;
-    if (blocks >= (1LL << 31)) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_resample3d: grid too large");
-    const dim3 grid(static_cast<unsigned>(blocks)), block(kRowsPerBlock * kLanes);
-    const size_t lds = (n_cp > 0 && n_cp <= kMaxCpLds) ? static_cast<size_t>(n_cp) * sizeof(float) : 0;
-    if (pv.cp != nullptr)
-      hipLaunchKernelGGL((resample_kernel<true, 2, 1>), grid, block, lds, s, pv);
-    else
-      hipLaunchKernelGGL((resample_kernel<false, 2, 1>), grid, block, lds, s, pv);
-    if (a.n_images == 0 && spl.n_images == 0) return check_launch("tio_resample3d");
-  }
-  if (spl.n_images > 0) {
-    spl.tiles_k = (spl.Ko + kLanes - 1) / kLanes;
-    spl.tiles_j = (spl.Jo + kRowsPerBlock - 1) / kRowsPerBlock;
-    spl.tiles_i = (spl.Io + kTileI - 1) / kTileI;
-    const int64_t blocks = static_cast<int64_t>(spl.B) * spl.tiles_i * spl.tiles_j * spl.tiles_k;
-    if (blocks >= (1LL << 31)) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_resample3d: grid too large");
-    if (static_cast<int64_t>(spl.I) * spl.J * spl.K >= (1LL << 31)) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_resample3d: volume too large");
-    const dim3 grid(static_cast<unsigned>(blocks)), block(kRowsPerBlock * kLanes);
-    const size_t lds = (n_cp > 0 && n_cp <= kMaxCpLds) ? static_cast<size_t>(n_cp) * sizeof(float) : 0;
-    if (spl.cp != nullptr)
-      hipLaunchKernelGGL((resample_kernel<true, 0, 2>), grid, block, lds, s, spl);
-    else
-      hipLaunchKernelGGL((resample_kernel<false, 0, 2>), grid, block, lds, s, spl);
-    if (a.n_images == 0) return check_launch("tio_resample3d");
-  }
-
-  // Path: LDS-staged bricks whenever a trilinear image is present (the 8-tap gather is
-  // what the staging removes); pure nearest launches keep the one-load gather kernel.
+struct FloatRoad {
+  FloatRoadKind kind = kRoadGather;
+  int variant = 0;          // brick roads: the brick shape (TIO_TILE_VARIANT; 0: 16 x 16 x 16)
+  bool exact_lerp = false;  // lean exact: ATen's interpolation order (bit-identical to the brick kernel) instead of TIGHT's fused lerps
+  int64_t bricks = 0;       // 16^3 bricks of the launch (planned roads: the plan's items)
+  size_t lds = 0;           // dynamic LDS of the sampling kernel, bytes
+  size_t plan_need = 0;     // bytes of the plan the road starts from (0: it does not)
+  int cp_lds = 0, tile_cap = 0, ablate = 0, fill_recheck = 0, dma_packed = 0, plan_multi = 0;  // what apply_road copies into ResampleArgs
+  int interleave = 0, pair = 0;  // launch_lean: TIO_LEAN_INTERLEAVE, TIO_LEAN_PAIR (A/B)
+};
+FloatRoad choose_float_road(const tio_resample_geom& geom, const ResampleArgs& a, const FloatGroup& g, const EnvSwitches& env) {
+  FloatRoad r;
+  // LDS-staged bricks whenever a trilinear image is present (the 8-tap gather is what the staging removes); pure nearest launches keep the one-load gather kernel.
   // TIO_RESAMPLE_PATH=gather|tile overrides (A/B tests compare the two bit for bit).
-  bool use_tile = a.any_linear != 0 && !any_adjoint;  // the adjoint scatters to global memory: gather kernel
+  bool use_tile = a.any_linear != 0;
   if (env.resample_path == 1) use_tile = false;
   if (env.resample_path == 2) use_tile = true;
-  if (any_adjoint) use_tile = false;
+  if (g.any_adjoint) use_tile = false;  // the adjoint scatters to global memory: gather kernel
   if (static_cast<int64_t>(a.Jo) * a.Ko * 8 >= (1LL << 31)) use_tile = false;  // 32-bit byte offsets inside one output plane
-  if (n_in >= (1LL << 30)) use_tile = false;  // 32-bit byte offsets inside one input channel (f32 brick DMA)
-  if (use_tile) {
-    a.fill_recheck = env.fast_fill_recheck;
-    a.any_fill = 0;
-    for (int i = 0; i < a.n_images; i++) a.any_fill |= a.img[i].fill != nullptr ? 1 : 0;
-    const int variant = env.tile_variant;
-    int cap = env.tile_lds_floats;
-    a.ablate = env.tile_ablate;
-    a.cp_lds = (n_cp > 0 && n_cp <= kMaxCpLds) ? ((n_cp + 3) & ~3) : 0;
-    // default brick budget: whatever lets kTileBlocksPerCU blocks share the CU's 160 KiB
-    // (minus 2 KiB: the hardware allocates LDS in granules, an exact third does not fit three times)
-    const int bpc = variant == 3 ? 2 : ((variant == 2 || variant == 4) ? 4 : kTileBlocksPerCU);  // resident blocks the variant is built for
-    if (cap <= 0) cap = kLdsFloatsPerCU / bpc - 512 - a.cp_lds - kTileRedInts;
-    const int max_cap = kLdsFloatsPerCU - a.cp_lds - kTileRedInts;
-    a.tile_cap = cap < kTileMinCap ? kTileMinCap : (cap > max_cap ? max_cap : cap);
-    const size_t lds = static_cast<size_t>(a.cp_lds + kTileRedInts + a.tile_cap) * sizeof(float);
-#define TIO_TILE_LAUNCH(EL, DM, TI, TJ, TK, OCC)                                                              \
-  {                                                                                                      \
-    a.tiles_k = (a.Ko + TK - 1) / TK;                                                                    \
-    a.tiles_j = (a.Jo + TJ - 1) / TJ;                                                                    \
-    a.tiles_i = (a.Io + TI - 1) / TI;                                                                    \
-    a.magic_k = a.tiles_k > 1 ? 0xFFFFFFFFu / a.tiles_k + 1u : 0u;                                       \
-    a.magic_j = a.tiles_j > 1 ? 0xFFFFFFFFu / a.tiles_j + 1u : 0u;                                       \
-    a.magic_i = a.tiles_i > 1 ? 0xFFFFFFFFu / a.tiles_i + 1u : 0u;                                       \
-    const int64_t blocks = static_cast<int64_t>(a.B) * a.tiles_i * a.tiles_j * a.tiles_k;                \
-    if (blocks >= (1LL << 31)) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_resample3d: grid too large");  \
-    auto kernel = resample_tile_kernel<EL, DM, TI, TJ, TK, OCC>;                                            \
-    if (lds > 48 * 1024) {                                                                               \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                              static_cast<int>(lds)) != hipSuccess)                                      \
-        return fail(TIO_ERR_LAUNCH, "tio_resample3d: cannot reserve %zu bytes of LDS", lds);             \
-    }                                                                                                    \
-    hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(blocks)), dim3(TJ* TK), lds, s, a,             \
-                       (TI == 16 && TJ == 16 && TK == 16) ? plan_exact : static_cast<const int*>(nullptr)); \
-  }
-#define TIO_TILE_SHAPE(TI, TJ, TK, OCC)                                                  \
-  {                                                                                 \
-    if (a.cp != nullptr) {                                                          \
-      if (dtmode == 0) TIO_TILE_LAUNCH(true, 0, TI, TJ, TK, OCC)                        \
-      else if (dtmode == 1) TIO_TILE_LAUNCH(true, 1, TI, TJ, TK, OCC)                   \
-      else TIO_TILE_LAUNCH(true, 2, TI, TJ, TK, OCC)                                    \
-    } else {                                                                        \
-      if (dtmode == 0) TIO_TILE_LAUNCH(false, 0, TI, TJ, TK, OCC)                       \
-      else if (dtmode == 1) TIO_TILE_LAUNCH(false, 1, TI, TJ, TK, OCC)                  \
-      else TIO_TILE_LAUNCH(false, 2, TI, TJ, TK, OCC)                                   \
-    }                                                                               \
-  }
-#define TIO_TILE_SHAPE_F32(TI, TJ, TK, OCC) /* experimental shapes: float32 launches only */ \
-  {                                                                                 \
-    if (dtmode != 0) {                                                              \
-      TIO_TILE_SHAPE(16, 16, 16, 3)                                                 \
-    } else if (a.cp != nullptr) {                                                   \
-      TIO_TILE_LAUNCH(true, 0, TI, TJ, TK, OCC)                                         \
-    } else {                                                                        \
-      TIO_TILE_LAUNCH(false, 0, TI, TJ, TK, OCC)                                        \
-    }                                                                               \
-  }
-    // fast intensity path: float32 trilinear images only (nearest / label images need the exact coordinates)
-    const bool fast = geom->precision == TIO_PRECISION_FAST && dtmode == 0 && !a.any_nearest && variant == 0 &&
-                      !env.resample_exact;
-    // Round 5: the lean planned kernel with the reference's own coordinates (resample_lean_exact.hpp).  TIO_PRECISION_TIGHT:
-    // fused interpolation on exact coordinates / taps / fill decisions; TIO_PRECISION_EXACT: ATen's interpolation order too,
-    // bit-identical to the brick kernel below (TIO_EXACT_LEAN=0 keeps large exact launches on the brick kernel, =2 sends
-    // small ones to the lean kernel as well: A/B and tests).  Float32 trilinear images only, divisors the short division is
-    // proven for, unit spacing whenever a displacement is divided by it; everything else runs the exact brick kernel.
-    const bool tight = geom->precision == TIO_PRECISION_TIGHT && !env.resample_exact;  // (TIO_RESAMPLE_EXACT: the A/B switch forces ATen's interpolation order too)
-    const bool lean_exact = !fast && (tight || ((geom->precision == TIO_PRECISION_EXACT || geom->precision == TIO_PRECISION_TIGHT) && env.exact_lean != 0)) && dtmode == 0 &&
-                            !a.any_nearest && variant == 0 && a.ablate == 0 && a.short_div != 0 && (a.cp == nullptr || a.unit_spacing != 0);
-    if (fast || lean_exact) {
-      a.tiles_k = (a.Ko + 15) / 16; a.tiles_j = (a.Jo + 15) / 16; a.tiles_i = (a.Io + 15) / 16;
-      a.magic_k = a.tiles_k > 1 ? 0xFFFFFFFFu / a.tiles_k + 1u : 0u;
-      a.magic_j = a.tiles_j > 1 ? 0xFFFFFFFFu / a.tiles_j + 1u : 0u;
-      a.magic_i = a.tiles_i > 1 ? 0xFFFFFFFFu / a.tiles_i + 1u : 0u;
-      const int64_t blocks = static_cast<int64_t>(a.B) * a.tiles_i * a.tiles_j * a.tiles_k;
-      if (blocks >= (1LL << 31)) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_resample3d: grid too large");
-      // Planned bricks (resample_fast.hpp): a one-thread-per-brick planning kernel, then one block per brick that starts
-      // from its 64-byte descriptor.  Needs 16-byte rows for the LDS-DMA and control cells at least a brick wide (the
-      // box comes from <= 27 vertices); everything else — and TIO_FAST_KERNEL=brick, the A/B switch — runs the brick
-      // kernel's FAST instantiation with its in-kernel boxes.
-      // (small launches keep the single-kernel road: the planning kernel and the gap before the second launch cost
-      // ~10-15 us, more than the planned bricks save below ~12 k bricks; TIO_FAST_KERNEL=planned forces them)
-      const bool force_planned = lean_exact ? (env.fast_kernel == 2 || env.exact_lean == 2) : env.fast_kernel == 2;
-      bool planned = (lean_exact || env.fast_kernel != 1) && (a.K & 3) == 0 && (blocks >= kPlannedMinBricks || force_planned) && blocks < (1LL << 26);
-      for (int i = 0; i < a.n_images; i++) planned = planned && (reinterpret_cast<uintptr_t>(a.img[i].in) & 15) == 0;
-      // the caller expects boxes beyond the staging tile (tio_hip.h: TIO_GEOM_LARGE_BOXES): a planned brick whose box does not fit
-      // samples voxel by voxel from global memory, the brick kernels below split it into passes over its planes
-      // (round 6: the exact-coordinate lean road stages such bricks in passes itself — the hint only sends FAST launches elsewhere)
-      if ((geom->flags & (TIO_GEOM_LARGE_BOXES | TIO_GEOM_MOSTLY_LARGE_BOXES)) != 0 && !force_planned && !lean_exact) planned = false;
-      if (planned && a.cp != nullptr) {
-        const int n_ctl[3] = {a.ni, a.nj, a.nk}, n_vox[3] = {a.Io, a.Jo, a.Ko};
-        for (int d = 0; d < 3; d++)
-          if (n_ctl[d] > 2 && (n_vox[d] - 1) < 16 * (n_ctl[d] - 1)) planned = false;
-      }
-      if (planned) {
-        // one single-channel image (what a FAST intensity launch almost always is): the lean kernel (resample_fast.hpp),
-        // whose bricks may be 8 planes thick (half the tile: twice the blocks per CU)
-        const bool lean = env.planned_lean != 0 || lean_exact;
-        const int64_t items64 = blocks;
-        // the largest tile three blocks of which fit a CU: LDS is handed out in granules of 1 280 bytes here (measured: 13 440
-        // floats keep three blocks resident, 13 568 drop to two — profiles/r04_tile_cap.log); 300 floats more than the round-3
-        // value, which is 1.5 % of a fused affine + elastic launch (fewer bricks on the per-voxel road)
-        int cap_p = (kLdsFloatsPerCU / kTileBlocksPerCU) / 320 * 320;
-        if (env.tile_lds_floats > 0) cap_p = env.tile_lds_floats;
-        if (cap_p < kTileMinCap) cap_p = kTileMinCap;
-        if (cap_p > kLdsFloatsPerCU) cap_p = kLdsFloatsPerCU;
-        a.tile_cap = cap_p;
-        a.cp_lds = 0;
-        const size_t lds_p = static_cast<size_t>(cap_p) * sizeof(float);
-        const int n_items = static_cast<int>(items64);
-        // round 3: DMA instructions that cover rows across x-plane boundaries (resample_fast.hpp: stream_stage_packed);
-        // TIO_DMA_PACKED=0 switches them off in the general kernel (A/B)
-        a.dma_packed = env.dma_packed;
-        // (the exact-coordinate kernel stages bricks whose box exceeds the tile in passes over their planes: pass boxes behind the descriptors)
-        // — on the hint of a caller who holds the mappings (TIO_GEOM_LARGE_BOXES): the second kernel sits BEHIND the first on the stream,
-        // ~6 - 15 us that a launch without such bricks should not pay (measured +0 ... +3.7 % on the bench's launches when it was
-        // unconditional: profiles/r06_resample.md); without the hint such bricks sample voxel by voxel, as until round 5
-        // (TIO_GEOM_MOSTLY_LARGE_BOXES: plan_multi = 2 — every block of ONE launch runs the body with the pass switches, nothing is listed)
-        a.plan_multi = (lean_exact && env.lean_multi != 0) ? ((geom->flags & TIO_GEOM_MOSTLY_LARGE_BOXES) != 0 ? 2 : ((geom->flags & TIO_GEOM_LARGE_BOXES) != 0 ? 1 : 0)) : 0;
-        // [header: kPlanHeaderInts ints] [B x 16 floats] [n_items descriptors] ( [n_items x 4 pass boxes] [the list of multi-pass bricks] )
-        const size_t plan_list_at = static_cast<size_t>(a.B) * 16 + static_cast<size_t>(n_items) * (kDescInts + kPassInts * kPassesPerBrick);  // (ints behind the header)
-        const size_t plan_need = (kPlanHeaderInts + (a.plan_multi ? plan_list_at + ((static_cast<size_t>(n_items) + 3) & ~static_cast<size_t>(3))
-                                                                    : static_cast<size_t>(a.B) * 16 + static_cast<size_t>(n_items) * kDescInts)) * sizeof(int);
-        if (mode == kPlanQuery) { *plan_bytes = static_cast<int64_t>(plan_need); return TIO_OK; }
-        PlanLease lease;
-        int* plan = nullptr;
-        bool planned_ahead = false;
-        if (mode == kPlanOnly) {
-          if (plan_out == nullptr || plan_out_bytes < static_cast<int64_t>(plan_need) || (reinterpret_cast<uintptr_t>(plan_out) & 15) != 0)
-            return fail(TIO_ERR_INVALID_ARGUMENT, "tio_resample3d_plan: the plan needs %zu bytes, 16-byte aligned", plan_need);
-          plan = plan_out + kPlanHeaderInts;
-        } else if (geom->plan_dev != nullptr && geom->plan_bytes >= static_cast<int64_t>(plan_need) &&
-                   (reinterpret_cast<uintptr_t>(geom->plan_dev) & 15) == 0) {
-          plan = static_cast<int*>(const_cast<void*>(geom->plan_dev)) + kPlanHeaderInts;  // made ahead by tio_resample3d_plan: no planning kernel on this stream
-          planned_ahead = true;
-        } else {
-          lease = plan_workspace(s, plan_need);
-          if (lease.ptr == nullptr) return fail(TIO_ERR_LAUNCH, "tio_resample3d: cannot allocate the brick plan");
-          plan = lease.ptr + kPlanHeaderInts;  // (the lease is released when this function returns: after both kernels are enqueued)
-        }
-        if (!planned_ahead) {
-          const int plan_lanes = plan_group(a.cp != nullptr);  // lanes per brick
-          const int plan_threads = n_items * plan_lanes > a.B ? n_items * plan_lanes : a.B;
-          const dim3 plan_grid((plan_threads + 255) / 256);
-          // the header of the multi-pass bricks' list (length, cursor, done count) is zero between launches: the leased workspace is
-          // zeroed when it is allocated and the last walker of a call's last launch leaves zeros; a caller's buffer is zeroed here —
-          // and keeps its length after every call it is handed to (la.last_use below: a plan made ahead serves any number of calls)
-          if (a.plan_multi && mode == kPlanOnly && hipMemsetAsync(plan - kPlanHeaderInts, 0, kPlanHeaderInts * sizeof(int), s) != hipSuccess)
-            return fail(TIO_ERR_LAUNCH, "tio_resample3d_plan: cannot reset the brick plan");
-          if (a.cp != nullptr) hipLaunchKernelGGL((plan_bricks_kernel<true, 16, 16, 16>), plan_grid, dim3(256), 0, s, a, plan, n_items);
-          else hipLaunchKernelGGL((plan_bricks_kernel<false, 16, 16, 16>), plan_grid, dim3(256), 0, s, a, plan, n_items);
-        }
-        if (mode == kPlanOnly) { *plan_bytes = static_cast<int64_t>(plan_need); return check_launch("tio_resample3d_plan"); }
-        // the folded minimum: kMinSlots keys per channel that asked for it (common.hpp: min_workspace, all ones between
-        // launches), finished by min_finish_kernel behind the sampling kernel
-        uint32_t* min_keys = nullptr;
-        MinOuts min_outs{};
-        int min_channels = 0;
-        {
-          for (int i = 0; i < a.n_images; i++) min_channels += a.img[i].out_min != nullptr ? a.img[i].channels : 0;
-          if (min_channels > 0 && min_channels <= kMinChannels && pv.n_images == 0) {
-            int cap = 0;
-            min_keys = min_workspace(s, min_channels * kMinSlots, &cap, /*kind=*/1);  // its own array: tio_channel_min may be enqueued between this launch's two kernels
-            if (min_keys == nullptr) return fail(TIO_ERR_LAUNCH, "tio_resample3d: cannot allocate the reduction workspace");
-            int slot = 0;
-            for (int i = 0; i < a.n_images; i++)
-              if (a.img[i].out_min != nullptr) {
-                a.img[i].min_keys = min_keys + slot * kMinSlots;
-                for (int c = 0; c < a.img[i].channels; c++) min_outs.p[slot + c] = a.img[i].out_min + c;
-                slot += a.img[i].channels;
-              }
-            *folded = true;
-          } else {
-            min_channels = 0;
-            for (int i = 0; i < a.n_images; i++) a.img[i].out_min = nullptr;
-          }
-        }
-        auto launch_planned = [&](auto kernel) -> int {
-          if (lds_p > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                      static_cast<int>(lds_p)) != hipSuccess)
-            return fail(TIO_ERR_LAUNCH, "tio_resample3d: cannot reserve %zu bytes of LDS", lds_p);
-          hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(n_items)), dim3(256), lds_p, s, a, static_cast<const int*>(plan));
-          if (min_channels > 0)
-            hipLaunchKernelGGL(min_finish_kernel, dim3(static_cast<unsigned>(min_channels)), dim3(kMinSlots), 0, s, min_keys, min_outs, min_channels);
-          return check_launch("tio_resample3d");
-        };
-        if (lean) {
-          LeanArgs la{};
-          la.plan = plan; la.cp = a.cp;
-          la.I = a.I; la.J = a.J; la.K = a.K; la.Io = a.Io; la.Jo = a.Jo; la.Ko = a.Ko;
-          la.B = a.B; la.n_items = n_items;
-          la.bricks_per_element = static_cast<unsigned>(a.tiles_i) * a.tiles_j * a.tiles_k;
-          la.bpe_magic = la.bricks_per_element > 1 ? 0xFFFFFFFFu / la.bricks_per_element + 1u : 0u;
-          la.ni = a.ni; la.nj = a.nj; la.nk = a.nk; la.cp_batched = a.cp_batched;
-          la.sci = a.scale_i; la.scj = a.scale_j; la.sck = a.scale_k;
-          for (int e = 0; e < 3; e++) la.dsc[e] = a.rsp[e] * (a.affine_first ? a.half_h[e] / a.dh[e] : 1.0f);
-          la.hx = a.size_m1[0]; la.hy = a.size_m1[1]; la.hz = a.size_m1[2];
-          la.affine_first = a.affine_first; la.ablate = a.ablate;
-          la.mapping = a.mapping; la.mapping_batched = a.mapping_batched; la.unit_spacing = a.unit_spacing; la.fill_recheck = a.fill_recheck;
-          for (int e = 0; e < 3; e++) { la.sp[e] = a.sp[e]; la.rsp[e] = a.rsp[e]; la.den[e] = a.den[e]; la.rden[e] = a.rden[e]; }
-          for (int e = 0; e < 3; e++) { la.dh[e] = a.dh[e]; la.rdh[e] = a.rdh[e]; la.half_h[e] = a.half_h[e]; }
-          la.interleave = env.lean_interleave;
-          la.tile_floats = cap_p;
-          auto kernel = a.cp != nullptr ? resample_planned_lean_kernel<true, 16, 16, 16, 3> : resample_planned_lean_kernel<false, 16, 16, 16, 3>;
-          if (lean_exact) {  // the reference's coordinates; `tight`: fused lerps, else ATen's order (bit-identical to the brick kernel)
-            if (tight) {
-              if (min_channels > 0) kernel = a.cp != nullptr ? resample_lean_exact_kernel<true, false, 3, true> : resample_lean_exact_kernel<false, false, 3, true>;
-              else kernel = a.cp != nullptr ? resample_lean_exact_kernel<true, false, 3> : resample_lean_exact_kernel<false, false, 3>;
-            } else {
-              if (min_channels > 0) kernel = a.cp != nullptr ? resample_lean_exact_kernel<true, true, 3, true> : resample_lean_exact_kernel<false, true, 3, true>;
-              else kernel = a.cp != nullptr ? resample_lean_exact_kernel<true, true, 3> : resample_lean_exact_kernel<false, true, 3>;
-            }
-          } else if (la.ablate != 0)  // TIO_TILE_ABLATE: the instrumented instantiation (experiments only)
-            kernel = a.cp != nullptr ? resample_planned_lean_kernel<true, 16, 16, 16, 3, true> : resample_planned_lean_kernel<false, 16, 16, 16, 3, true>;
-          else if (min_channels > 0)  // the folded minimum: the instantiation whose element-0 bricks track what they store
-            kernel = a.cp != nullptr ? resample_planned_lean_kernel<true, 16, 16, 16, 3, false, true> : resample_planned_lean_kernel<false, 16, 16, 16, 3, false, true>;
-          const size_t lds_launch = lds_p;
-          const unsigned grid_launch = static_cast<unsigned>(n_items), block_launch = 256;
-          // ... and, behind an exact-coordinate launch, the kernel whose blocks walk the planner's list of multi-pass bricks (boxes beyond
-          // the tile: staged in halves / quarters of their planes) — three per CU, leaving at once when the list is empty
-          auto kernel_multi = a.cp != nullptr ? resample_lean_exact_multi_kernel<true, false> : resample_lean_exact_multi_kernel<false, false>;
-          if (a.plan_multi == 1) {
-            if (tight) {
-              if (min_channels > 0) kernel_multi = a.cp != nullptr ? resample_lean_exact_multi_kernel<true, false, true> : resample_lean_exact_multi_kernel<false, false, true>;
-            } else if (min_channels > 0) {
-              kernel_multi = a.cp != nullptr ? resample_lean_exact_multi_kernel<true, true, true> : resample_lean_exact_multi_kernel<false, true, true>;
-            } else {
-              kernel_multi = a.cp != nullptr ? resample_lean_exact_multi_kernel<true, true> : resample_lean_exact_multi_kernel<false, true>;
-            }
-          }
-          if (a.plan_multi == 2) {  // most bricks need passes: ONE launch of the body that knows them
-            if (tight) kernel = min_channels > 0 ? (a.cp != nullptr ? resample_lean_exact_all_kernel<true, false, true> : resample_lean_exact_all_kernel<false, false, true>)
-                                                 : (a.cp != nullptr ? resample_lean_exact_all_kernel<true, false> : resample_lean_exact_all_kernel<false, false>);
-            else kernel = min_channels > 0 ? (a.cp != nullptr ? resample_lean_exact_all_kernel<true, true, true> : resample_lean_exact_all_kernel<false, true, true>)
-                                           : (a.cp != nullptr ? resample_lean_exact_all_kernel<true, true> : resample_lean_exact_all_kernel<false, true>);
-          }
-          const bool walk_list = a.plan_multi == 1;
-          const unsigned grid_multi = static_cast<unsigned>(std::min<int64_t>(n_items, 3 * 256));
-          if (lds_launch > 48 * 1024 && (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                             static_cast<int>(lds_launch)) != hipSuccess ||
-                                         (walk_list && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel_multi), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                                              static_cast<int>(lds_launch)) != hipSuccess)))
-            return fail(TIO_ERR_LAUNCH, "tio_resample3d: cannot reserve %zu bytes of LDS", lds_launch);
-          int launches_left = 0;
-          for (int i = 0; i < a.n_images; i++) launches_left += a.img[i].channels;
-          // round 6: two channels per launch (resample_lean_exact_pair_kernel: one descriptor round trip, one set of control planes, ONE
-          // coordinate chain for both) where the launch is an exact-coordinate one without multi-pass bricks and without a folded
-          // minimum — a subject's float32 images share their geometry — and the call's label channel, if one waits (label_rides), with the
-          // last of them (resample_lean_exact_label_kernel).  TIO_LEAN_PAIR=0: one launch per channel, TIO_LEAN_LABEL=0: the label map's own kernel (A/B)
-          const bool label_here = static_cast<bool>(label_rides.launch) && lean_exact && a.plan_multi == 0 && min_channels == 0 && a.passthrough == nn.passthrough;
-          if (lean_exact && a.plan_multi == 0 && min_channels == 0 && ((launches_left >= 2 && env.lean_pair != 0) || label_here)) {
-            const bool pairs = launches_left >= 2 && env.lean_pair != 0;
-            auto kernel_pair = tight ? (a.cp != nullptr ? resample_lean_exact_pair_kernel<true, false> : resample_lean_exact_pair_kernel<false, false>)
-                                     : (a.cp != nullptr ? resample_lean_exact_pair_kernel<true, true> : resample_lean_exact_pair_kernel<false, true>);
-            auto kernel_label_pair = tight ? (a.cp != nullptr ? resample_lean_exact_label_kernel<true, false, true> : resample_lean_exact_label_kernel<false, false, true>)
-                                           : (a.cp != nullptr ? resample_lean_exact_label_kernel<true, true, true> : resample_lean_exact_label_kernel<false, true, true>);
-            auto kernel_label_one = tight ? (a.cp != nullptr ? resample_lean_exact_label_kernel<true, false, false> : resample_lean_exact_label_kernel<false, false, false>)
-                                          : (a.cp != nullptr ? resample_lean_exact_label_kernel<true, true, false> : resample_lean_exact_label_kernel<false, true, false>);
-            if (lds_launch > 48 * 1024 &&
-                (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel_pair), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_launch)) != hipSuccess ||
-                 (label_here && (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel_label_pair), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_launch)) != hipSuccess ||
-                                 hipFuncSetAttribute(reinterpret_cast<const void*>(kernel_label_one), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_launch)) != hipSuccess))))
-              return fail(TIO_ERR_LAUNCH, "tio_resample3d: cannot reserve %zu bytes of LDS", lds_launch);
-            if (label_here) { la.lab_in = nn.img[0].in; la.lab_out = nn.img[0].out; la.lab_es = label_es; }
-            bool have_first = false;
-            for (int i = 0; i < a.n_images; i++) {
-              const ImgArgs& g = a.img[i];
-              for (int c = 0; c < g.channels; c++) {
-                const float* in_c = static_cast<const float*>(g.in) + static_cast<int64_t>(c) * n_in;
-                float* out_c = static_cast<float*>(g.out) + static_cast<int64_t>(c) * n_out;
-                const float* fill_c = g.fill != nullptr ? g.fill + c : nullptr;
-                const int64_t in_stride = static_cast<int64_t>(g.channels) * n_in, out_stride = static_cast<int64_t>(g.channels) * n_out;
-                --launches_left;
-                if (pairs && !have_first && launches_left > 0) {  // (an odd channel out is launched alone, below)
-                  la.in = in_c; la.out = out_c; la.fill = fill_c; la.in_stride = in_stride; la.out_stride = out_stride;
-                  have_first = true;
-                  continue;
-                }
-                la.last_use = !planned_ahead && launches_left == 0;
-                la.min_keys = nullptr;
-                const bool with_label = label_here && launches_left == 0;
-                if (have_first) {
-                  la.in2 = in_c; la.out2 = out_c; la.fill2 = fill_c; la.in_stride2 = in_stride; la.out_stride2 = out_stride;
-                  if (with_label) hipLaunchKernelGGL(kernel_label_pair, dim3(grid_launch), dim3(block_launch), lds_launch, s, la);
-                  else hipLaunchKernelGGL(kernel_pair, dim3(grid_launch), dim3(block_launch), lds_launch, s, la);
-                  have_first = false;
-                } else {
-                  la.in = in_c; la.out = out_c; la.fill = fill_c; la.in_stride = in_stride; la.out_stride = out_stride;
-                  if (with_label) hipLaunchKernelGGL(kernel_label_one, dim3(grid_launch), dim3(block_launch), lds_launch, s, la);
-                  else hipLaunchKernelGGL(kernel, dim3(grid_launch), dim3(block_launch), lds_launch, s, la);
-                }
-              }
-            }
-            if (label_here) label_rides.launch = nullptr;  // (taken along)
-            return check_launch("tio_resample3d");
-          }
-          // one plan, one launch per channel of every image (the geometry, hence the plan, is shared)
-          for (int i = 0; i < a.n_images; i++) {
-            const ImgArgs& g = a.img[i];
-            la.in_stride = static_cast<int64_t>(g.channels) * n_in;
-            la.out_stride = static_cast<int64_t>(g.channels) * n_out;
-            for (int c = 0; c < g.channels; c++) {
-              la.in = static_cast<const float*>(g.in) + static_cast<int64_t>(c) * n_in;
-              la.out = static_cast<float*>(g.out) + static_cast<int64_t>(c) * n_out;
-              la.fill = g.fill != nullptr ? g.fill + c : nullptr;
-              la.min_keys = (min_channels > 0 && g.min_keys != nullptr) ? g.min_keys + c * kMinSlots : nullptr;
-              la.last_use = --launches_left == 0 && !planned_ahead;
-              hipLaunchKernelGGL(kernel, dim3(grid_launch), dim3(block_launch), lds_launch, s, la);
-              if (walk_list) hipLaunchKernelGGL(kernel_multi, dim3(grid_multi), dim3(block_launch), lds_launch, s, la);
-            }
-          }
-          if (min_channels > 0)
-            hipLaunchKernelGGL(min_finish_kernel, dim3(static_cast<unsigned>(min_channels)), dim3(kMinSlots), 0, s, min_keys, min_outs, min_channels);
-          return check_launch("tio_resample3d");
-        }
-        if (a.cp != nullptr) return launch_planned(resample_planned_kernel<true, 16, 16, 16, 3>);
-        return launch_planned(resample_planned_kernel<false, 16, 16, 16, 3>);
-      }
-      // (a TIGHT / EXACT launch the lean kernel does not take — too small, unaligned — falls through to the exact brick kernel)
-      if (fast) {
-        if (mode != kPlanNone) return TIO_OK;  // a FAST launch of in-kernel boxes: no plan
-        auto launch_fast = [&](auto kernel) -> int {
-          if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     static_cast<int>(lds)) != hipSuccess)
-            return fail(TIO_ERR_LAUNCH, "tio_resample3d: cannot reserve %zu bytes of LDS", lds);
-          hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), lds, s, a, static_cast<const int*>(nullptr));
-          return check_launch("tio_resample3d");
-        };
-        if (a.cp != nullptr) return launch_fast(resample_tile_kernel<true, 0, 16, 16, 16, 3, true>);
-        return launch_fast(resample_tile_kernel<false, 0, 16, 16, 16, 3, true>);
-      }
+  if (static_cast<int64_t>(a.I) * a.J * a.K >= (1LL << 30)) use_tile = false;  // 32-bit byte offsets inside one input channel (f32 brick DMA)
+  if (!use_tile) return r;
+  r.kind = kRoadBrick;
+  r.variant = env.tile_variant;
+  r.ablate = env.tile_ablate;
+  r.fill_recheck = env.fast_fill_recheck;
+  r.cp_lds = control_points_fit_lds(a) ? ((control_floats(a) + 3) & ~3) : 0;
+  // default brick budget: whatever lets kTileBlocksPerCU blocks share the CU's 160 KiB (minus 2 KiB: LDS is allocated in granules, an exact third does not fit three times)
+  const int bpc = r.variant == 3 ? 2 : ((r.variant == 2 || r.variant == 4) ? 4 : kTileBlocksPerCU);  // resident blocks the variant is built for
+  const int cap = env.tile_lds_floats > 0 ? env.tile_lds_floats : kLdsFloatsPerCU / bpc - 512 - r.cp_lds - kTileRedInts;
+  const int max_cap = kLdsFloatsPerCU - r.cp_lds - kTileRedInts;
+  r.tile_cap = cap < kTileMinCap ? kTileMinCap : (cap > max_cap ? max_cap : cap);
+  r.lds = static_cast<size_t>(r.cp_lds + kTileRedInts + r.tile_cap) * sizeof(float);
+  r.bricks = static_cast<int64_t>(a.B) * ((a.Io + 15) / 16) * ((a.Jo + 15) / 16) * ((a.Ko + 15) / 16);
+  const size_t plan_plain = static_cast<size_t>(a.B) * 16 + static_cast<size_t>(r.bricks) * kDescInts;  // (ints behind the header)
+  // fast intensity path: float32 trilinear images only (nearest / label images need the exact coordinates)
+  const bool fast = geom.precision == TIO_PRECISION_FAST && g.dtmode == 0 && !a.any_nearest && r.variant == 0 && !env.resample_exact;
+  // The lean planned kernel with the reference's own coordinates (resample_lean_exact.hpp).  TIO_PRECISION_TIGHT: fused interpolation on exact coordinates / taps / fill
+  // decisions; TIO_PRECISION_EXACT: ATen's interpolation order too, bit-identical to the brick kernel (TIO_EXACT_LEAN=0 keeps large exact launches on the brick kernel, =2
+  // sends small ones to the lean kernel as well: A/B and tests).  Float32 trilinear images only, divisors the short division is proven for, unit spacing whenever a
+  // displacement is divided by it; everything else runs the exact brick kernel.
+  const bool tight = geom.precision == TIO_PRECISION_TIGHT && !env.resample_exact;  // (TIO_RESAMPLE_EXACT: the A/B switch forces ATen's interpolation order too)
+  const bool lean_exact = !fast && (tight || ((geom.precision == TIO_PRECISION_EXACT || geom.precision == TIO_PRECISION_TIGHT) && env.exact_lean != 0)) &&
+                          g.dtmode == 0 && !a.any_nearest && r.variant == 0 && r.ablate == 0 && a.short_div != 0 && (a.cp == nullptr || a.unit_spacing != 0);
+  if (fast || lean_exact) {
+    // Planned bricks (resample_fast.hpp): a planning kernel, then one block per brick that starts from its 64-byte descriptor. Needs 16-byte rows for the LDS-DMA and
+    // control cells at least a brick wide (the box comes from <= 27 vertices); small launches keep the single-kernel road (the planning kernel and the gap before the
+    // second launch cost ~10-15 us, more than the planned bricks save below ~12 k bricks).  TIO_FAST_KERNEL=planned forces them, =brick keeps FAST launches off them (A/B).
+    const bool force_planned = lean_exact ? (env.fast_kernel == 2 || env.exact_lean == 2) : env.fast_kernel == 2;
+    bool planned = (lean_exact || env.fast_kernel != 1) && (a.K & 3) == 0 && (r.bricks >= kPlannedMinBricks || force_planned) && r.bricks < (1LL << 26) && g.rows16;
+    // the caller expects boxes beyond the staging tile (tio_hip.h: TIO_GEOM_LARGE_BOXES): a planned FAST brick whose box does not fit samples voxel by voxel, the brick
+    // kernel splits it into passes over its planes — the hint sends FAST launches there; the lean exact road stages such bricks in passes itself (plan_multi) and stays
+    if ((geom.flags & (TIO_GEOM_LARGE_BOXES | TIO_GEOM_MOSTLY_LARGE_BOXES)) != 0 && !force_planned && !lean_exact) planned = false;
+    if (planned && a.cp != nullptr) {
+      const int n_ctl[3] = {a.ni, a.nj, a.nk}, n_vox[3] = {a.Io, a.Jo, a.Ko};
+      for (int d = 0; d < 3; d++)
+        if (n_ctl[d] > 2 && (n_vox[d] - 1) < 16 * (n_ctl[d] - 1)) planned = false;
     }
-    // Large affine-only exact launches of 16^3 bricks are planned too (resample_tile.hpp: the planned box only decides what
-    // is staged; the corner evaluation and its reductions leave the head of every block); TIO_EXACT_PLAN=0 switches it off,
-    // =2 forces it for small launches (A/B, tests).
-    const int* plan_exact = nullptr;
-    PlanLease exact_lease;  // held until the brick kernel is enqueued (end of this function)
-    {
-      // Measured (8 x 256^3): affine 0.497 -> 0.478 ms; elastic launches LOSE (0.588 -> 0.610: 27 vertices with their
-      // control-point reads per brick cost the planner more than the brick kernel's own reduction), and so do small ones.
-      // (Round 3, with the 32-lanes-per-brick planner: elastic 0.604 -> 0.622 ms, affine + elastic 0.666 -> 0.662: the exact
-      // elastic kernel is bound by its coordinate chain, not by what precedes it — profiles/r03_exp23_native.log.)
-      const bool want = variant == 0 && a.ablate == 0 && a.cp == nullptr && env.exact_plan != 0 &&
-                        (static_cast<int64_t>(a.B) * ((a.Io + 15) / 16) * ((a.Jo + 15) / 16) * ((a.Ko + 15) / 16) >= kPlannedMinBricks ||
-                         env.exact_plan == 2);
-      if (want) {
-        a.tiles_k = (a.Ko + 15) / 16; a.tiles_j = (a.Jo + 15) / 16; a.tiles_i = (a.Io + 15) / 16;
-        a.magic_k = a.tiles_k > 1 ? 0xFFFFFFFFu / a.tiles_k + 1u : 0u;
-        a.magic_j = a.tiles_j > 1 ? 0xFFFFFFFFu / a.tiles_j + 1u : 0u;
-        a.magic_i = a.tiles_i > 1 ? 0xFFFFFFFFu / a.tiles_i + 1u : 0u;
-        const int64_t items64 = static_cast<int64_t>(a.B) * a.tiles_i * a.tiles_j * a.tiles_k;
-        if (items64 < (1LL << 26)) {
-          const int n_items = static_cast<int>(items64);
-          // (every plan starts behind kPlanHeaderInts ints — the list header of the exact-coordinate lean road, which shares the leased
-          // workspace of the stream with this one and must find it zero)
-          const size_t plan_need = (kPlanHeaderInts + static_cast<size_t>(a.B) * 16 + static_cast<size_t>(n_items) * kDescInts) * sizeof(int);
-          if (mode == kPlanQuery) { *plan_bytes = static_cast<int64_t>(plan_need); return TIO_OK; }
-          int* plan = nullptr;
-          bool planned_ahead = false;
-          if (mode == kPlanOnly) {
-            if (plan_out == nullptr || plan_out_bytes < static_cast<int64_t>(plan_need) || (reinterpret_cast<uintptr_t>(plan_out) & 15) != 0)
-              return fail(TIO_ERR_INVALID_ARGUMENT, "tio_resample3d_plan: the plan needs %zu bytes, 16-byte aligned", plan_need);
-            plan = plan_out + kPlanHeaderInts;
-          } else if (geom->plan_dev != nullptr && geom->plan_bytes >= static_cast<int64_t>(plan_need) &&
-                     (reinterpret_cast<uintptr_t>(geom->plan_dev) & 15) == 0) {
-            plan = static_cast<int*>(const_cast<void*>(geom->plan_dev)) + kPlanHeaderInts;
-            planned_ahead = true;
-          } else {
-            exact_lease = plan_workspace(s, plan_need);
-            if (exact_lease.ptr == nullptr) return fail(TIO_ERR_LAUNCH, "tio_resample3d: cannot allocate the brick plan");
-            plan = exact_lease.ptr + kPlanHeaderInts;
-          }
-          if (!planned_ahead) {
-            const int plan_lanes = plan_group(a.cp != nullptr);  // lanes per brick
-            const int plan_threads = n_items * plan_lanes > a.B ? n_items * plan_lanes : a.B;
-            const dim3 plan_grid((plan_threads + 255) / 256);
-            if (a.cp != nullptr) hipLaunchKernelGGL((plan_bricks_kernel<true, 16, 16, 16>), plan_grid, dim3(256), 0, s, a, plan, n_items);
-            else hipLaunchKernelGGL((plan_bricks_kernel<false, 16, 16, 16>), plan_grid, dim3(256), 0, s, a, plan, n_items);
-          }
-          if (mode == kPlanOnly) { *plan_bytes = static_cast<int64_t>(plan_need); return check_launch("tio_resample3d_plan"); }
-          plan_exact = plan;
-        }
-      }
+    if (planned) {
+      r.kind = lean_exact ? kRoadLeanExact : (env.planned_lean != 0 ? kRoadPlannedLean : kRoadPlannedFast);
+      r.exact_lerp = !tight;
+      // the largest tile three blocks of which fit a CU: LDS is handed out in granules of 1 280 bytes here (measured: 13 440 floats keep three blocks resident, 13 568 drop
+      // to two — profiles/r04_tile_cap.log)
+      const int cap_p = env.tile_lds_floats > 0 ? env.tile_lds_floats : (kLdsFloatsPerCU / kTileBlocksPerCU) / 320 * 320;
+      r.tile_cap = cap_p < kTileMinCap ? kTileMinCap : (cap_p > kLdsFloatsPerCU ? kLdsFloatsPerCU : cap_p);
+      r.cp_lds = 0;
+      r.lds = static_cast<size_t>(r.tile_cap) * sizeof(float);
+      r.dma_packed = env.dma_packed;  // DMA instructions that cover rows across x-plane boundaries (TIO_DMA_PACKED=0: A/B)
+      r.interleave = env.lean_interleave;
+      r.pair = env.lean_pair;
+      // the exact-coordinate kernel stages bricks whose box exceeds the tile in passes over their planes (pass boxes behind the descriptors) — on the hint of a caller who
+      // holds the mappings: TIO_GEOM_LARGE_BOXES, plan_multi = 1, a second kernel BEHIND the first walks the planner's list of such bricks (~6 - 15 us that a launch
+      // without such bricks should not pay: profiles/r06_resample.md); TIO_GEOM_MOSTLY_LARGE_BOXES, plan_multi = 2: every block of ONE launch runs the body with the pass
+      // switches, nothing is listed.  Without the hint such bricks sample voxel by voxel.
+      if (lean_exact && env.lean_multi != 0)
+        r.plan_multi = (geom.flags & TIO_GEOM_MOSTLY_LARGE_BOXES) != 0 ? 2 : ((geom.flags & TIO_GEOM_LARGE_BOXES) != 0 ? 1 : 0);
+      // [header: kPlanHeaderInts ints] [B x 16 floats] [bricks x descriptors] ( [bricks x 4 pass boxes] [the list of multi-pass bricks] )
+      const size_t n = static_cast<size_t>(r.bricks);
+      const size_t plan_multi_ints = static_cast<size_t>(a.B) * 16 + n * (kDescInts + kPassInts * kPassesPerBrick) + ((n + 3) & ~static_cast<size_t>(3));
+      r.plan_need = (kPlanHeaderInts + (r.plan_multi ? plan_multi_ints : plan_plain)) * sizeof(int);
+      return r;
     }
-    if (mode != kPlanNone) return TIO_OK;  // bricks with in-kernel boxes: no plan
-    switch (variant) {
-      case 1: TIO_TILE_SHAPE_F32(16, 8, 32, 3) break;
-      case 2: TIO_TILE_SHAPE_F32(8, 8, 32, 4) break;
-      case 3: TIO_TILE_SHAPE_F32(8, 16, 32, 2) break;   /* 512 threads, 2 blocks per CU */
-      case 4: TIO_TILE_SHAPE_F32(8, 16, 16, 4) break;
-      default: TIO_TILE_SHAPE(16, 16, 16, 3) break;
+    // (a TIGHT / EXACT launch the lean kernel does not take — too small, unaligned — goes on to the exact brick kernel)
+    if (fast) {
+      r.kind = kRoadFastBrick;  // the brick kernel's FAST instantiation with its in-kernel boxes
+      return r;
     }
-#undef TIO_TILE_SHAPE_F32
-#undef TIO_TILE_SHAPE
-#undef TIO_TILE_LAUNCH
-    return check_launch("tio_resample3d");
   }
+  // Large affine-only exact launches of 16^3 bricks are planned too (resample_tile.hpp: the planned box only decides what is staged); TIO_EXACT_PLAN=0 switches it off, =2
+  // forces it for small launches (A/B, tests).  Measured (8 x 256^3): affine 0.497 -> 0.478 ms; elastic launches LOSE (0.588 -> 0.610: 27 vertices with their control-point
+  // reads per brick cost the planner more than the brick kernel's own reduction), and so do small ones.
+  if (r.variant == 0 && r.ablate == 0 && a.cp == nullptr && env.exact_plan != 0 && (r.bricks >= kPlannedMinBricks || env.exact_plan == 2) && r.bricks < (1LL << 26)) {
+    r.kind = kRoadPlannedBrick;
+    // (every plan starts behind kPlanHeaderInts ints: the list header of the lean exact road, which shares the stream's leased workspace and must find it zero)
+    r.plan_need = (kPlanHeaderInts + plan_plain) * sizeof(int);
+  }
+  return r;
+}
 
-  if (mode != kPlanNone) return TIO_OK;  // the gather kernel: no plan
-  a.tiles_k = (a.Ko + kLanes - 1) / kLanes;
-  a.tiles_j = (a.Jo + kRowsPerBlock - 1) / kRowsPerBlock;
-  a.tiles_i = (a.Io + kTileI - 1) / kTileI;
-  const int64_t blocks = static_cast<int64_t>(a.B) * a.tiles_i * a.tiles_j * a.tiles_k;
-  if (blocks >= (1LL << 31)) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_resample3d: grid too large");
-  const dim3 grid(static_cast<unsigned>(blocks)), block(kRowsPerBlock * kLanes);
-  const size_t lds = (n_cp > 0 && n_cp <= kMaxCpLds) ? static_cast<size_t>(n_cp) * sizeof(float) : 0;
-#define TIO_LAUNCH(EL, DM) hipLaunchKernelGGL((resample_kernel<EL, DM>), grid, block, lds, s, a)
-  if (a.cp != nullptr) {
-    if (dtmode == 0) TIO_LAUNCH(true, 0); else if (dtmode == 1) TIO_LAUNCH(true, 1); else TIO_LAUNCH(true, 2);
-  } else {
-    if (dtmode == 0) TIO_LAUNCH(false, 0); else if (dtmode == 1) TIO_LAUNCH(false, 1); else TIO_LAUNCH(false, 2);
+void apply_road(ResampleArgs& a, const FloatRoad& r) {
+  a.fill_recheck = r.fill_recheck; a.ablate = r.ablate; a.cp_lds = r.cp_lds; a.tile_cap = r.tile_cap;
+  a.dma_packed = r.dma_packed; a.plan_multi = r.plan_multi;
+  for (int i = 0; i < a.n_images && r.kind != kRoadGather; i++) a.any_fill |= a.img[i].fill != nullptr ? 1 : 0;
+}
+
+LeanArgs make_lean_args(const ResampleArgs& a, const FloatRoad& r, const int* plan, int n_items) {
+  LeanArgs la{};
+  la.plan = plan; la.cp = a.cp;
+  la.I = a.I; la.J = a.J; la.K = a.K; la.Io = a.Io; la.Jo = a.Jo; la.Ko = a.Ko;
+  la.B = a.B; la.n_items = n_items;
+  la.bricks_per_element = static_cast<unsigned>(a.tiles_i) * a.tiles_j * a.tiles_k;
+  la.bpe_magic = magic_u32(la.bricks_per_element);
+  la.ni = a.ni; la.nj = a.nj; la.nk = a.nk; la.cp_batched = a.cp_batched;
+  la.sci = a.scale_i; la.scj = a.scale_j; la.sck = a.scale_k;
+  for (int e = 0; e < 3; e++) la.dsc[e] = a.rsp[e] * (a.affine_first ? a.half_h[e] / a.dh[e] : 1.0f);
+  la.hx = a.size_m1[0]; la.hy = a.size_m1[1]; la.hz = a.size_m1[2];
+  la.affine_first = a.affine_first; la.ablate = a.ablate;
+  la.mapping = a.mapping; la.mapping_batched = a.mapping_batched; la.unit_spacing = a.unit_spacing; la.fill_recheck = a.fill_recheck;
+  for (int e = 0; e < 3; e++) { la.sp[e] = a.sp[e]; la.rsp[e] = a.rsp[e]; la.den[e] = a.den[e]; la.rden[e] = a.rden[e]; }
+  for (int e = 0; e < 3; e++) { la.dh[e] = a.dh[e]; la.rdh[e] = a.rdh[e]; la.half_h[e] = a.half_h[e]; }
+  la.interleave = r.interleave;
+  la.tile_floats = r.tile_cap;
+  return la;
+}
+
+// The label channel that may ride along the float images' last exact-coordinate launch (resample_lean_exact_label_kernel) instead of taking its own kernel.  es != 0: its
+// launch is pending — launch_lean takes it when its conditions hold (es = 0), otherwise resample3d_impl launches it before it returns, whatever road the images took.
+struct LabelRide {
+  int es = 0;  // element size of the pending label channel (0: none)
+  unsigned blocks = 0, lds = 0;
+};
+void launch_nearest_exact(const NearestArgs& nn, int es, unsigned blocks, unsigned lds, hipStream_t s) {
+  with_element_size(es, [&](auto size) {
+    with_bools([&](auto elastic) { hipLaunchKernelGGL((resample_nearest_exact_kernel<elastic.value, size.value>), dim3(blocks), dim3(256), lds, s, nn); }, nn.cp != nullptr);
+  });
+}
+
+// nearest images (label maps): one launch per element size present.  `short_div`: the float group's gate of the exact coordinates; `floats_alone`: float images follow and
+// nothing else does (the label channel may ride with them)
+int launch_nearest(NearestArgs& nn, bool short_div, bool floats_alone, const EnvSwitches& env, hipStream_t s, LabelRide* label) {
+  const bool rows = nn.Ko >= 48;  // bricks of 16 x 4 x 64 (a wave = one output row) unless the volume is narrower than that
+  unsigned blocks = 0;
+  if (const int st = set_tiles(nn, 16, rows ? 4 : 16, rows ? 64 : 16, &blocks)) return st;
+  nn.eps = env.has_nearest_eps ? env.nearest_eps : kNearestEps;  // (TIO_NEAREST_EPS: calibration runs only)
+  // without a fill rule the reference's own coordinates plane by plane (resample_nearest_exact_kernel; its gate is the float exact-coordinate kernel's: the short division,
+  // unit spacing under control points, rows of at least 48 voxels)
+  const bool exact = env.nearest_exact != 0 && nn.any_fill == 0 && rows && short_div && (nn.cp == nullptr || nn.unit_spacing != 0);
+  // resident blocks per CU through UNUSED dynamic LDS: without control points the kernel holds 61 registers (eight blocks per CU), and eight blocks' slanted input
+  // footprints evict one another's cache lines — three blocks per CU measured 0.236 -> 0.210 ms (int16) and 0.344 -> 0.286 (int32) on 8 x 256^3 at the bench's ranges, uint8
+  // 0.172 -> 0.177; with control points (95 registers, five blocks) the launch is arithmetic bound and loses from four blocks down (profiles/r06_labels.md).  TIO_NEAREST_LDS: A/B
+  const unsigned exact_lds = env.nearest_lds >= 0 ? static_cast<unsigned>(env.nearest_lds) : (nn.cp == nullptr ? 52000u : 0u);
+  for (int es = 1; es <= 8; es *= 2) {
+    bool present = false;
+    for (int i = 0; i < nn.n_images; i++) present = present || nn.img[i].es == es;
+    if (!present) continue;
+    // ... and its tail's: 24-bit offsets and buffer loads (I J <= 2^24, every channel below 2^32 bytes)
+    const int64_t n_in = static_cast<int64_t>(nn.I) * nn.J * nn.K, n_out = static_cast<int64_t>(nn.Io) * nn.Jo * nn.Ko;
+    const bool narrow = static_cast<int64_t>(nn.I) * nn.J <= (1 << 24) && static_cast<int64_t>(nn.K) * es < (1 << 24) &&
+                        n_in * es < (int64_t{1} << 32) - 16 && n_out * es < (int64_t{1} << 32) - 16;
+    if (exact && narrow && env.lean_label != 0 && nn.n_images == 1 && nn.img[0].channels == 1 && es <= 4 && floats_alone) {
+      label->es = es; label->blocks = blocks; label->lds = exact_lds;  // ONE plain label channel beside float images: it may ride
+    } else if (exact && narrow) {
+      launch_nearest_exact(nn, es, blocks, exact_lds, s);
+    } else {
+      with_element_size(es, [&](auto size) {
+        with_bools([&](auto elastic, auto wave_rows) {
+          hipLaunchKernelGGL((resample_nearest_kernel<elastic.value, size.value, wave_rows.value ? 4 : 16, wave_rows.value ? 64 : 16, 16>), dim3(blocks), dim3(256), 0, s, nn);
+        }, nn.cp != nullptr, rows);
+      });
+    }
   }
-#undef TIO_LAUNCH
+  return TIO_OK;
+}
+
+// the per-voxel gather kernel: a block walks kTileI output slabs of kRowsPerBlock rows of kLanes voxels, control points in LDS if they fit
+int launch_rows(RowsKernel kernel, ResampleArgs& a, hipStream_t s) {
+  unsigned blocks = 0;
+  if (const int st = set_tiles(a, kTileI, kRowsPerBlock, kLanes, &blocks)) return st;
+  const size_t lds = control_points_fit_lds(a) ? static_cast<size_t>(control_floats(a)) * sizeof(float) : 0;
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kRowsPerBlock * kLanes), lds, s, a);
+  return TIO_OK;
+}
+
+int launch_label_pv(ResampleArgs& pv, hipStream_t s) {
+  return launch_rows(with_bools([](auto elastic) -> RowsKernel { return resample_kernel<elastic.value, 2, 1>; }, pv.cp != nullptr), pv, s);
+}
+int launch_bspline(ResampleArgs& spl, hipStream_t s) {
+  return launch_rows(with_bools([](auto elastic) -> RowsKernel { return resample_kernel<elastic.value, 0, 2>; }, spl.cp != nullptr), spl, s);
+}
+
+int launch_gather(ResampleArgs& a, int dtmode, hipStream_t s) {
+  const RowsKernel kernel = with_bools([&](auto e) -> RowsKernel {
+    return dtmode == 0 ? resample_kernel<e.value, 0> : (dtmode == 1 ? resample_kernel<e.value, 1> : resample_kernel<e.value, 2>);
+  }, a.cp != nullptr);
+  const int status = launch_rows(kernel, a, s);
+  return status != TIO_OK ? status : check_launch("tio_resample3d");
+}
+
+// one block per brick of TI x TJ x TK voxels; only 16^3 bricks can start from a plan (nullptr: in-kernel boxes)
+int launch_brick_kernel(BrickKernel kernel, int ti, int tj, int tk, ResampleArgs& a, size_t lds, const int* plan, hipStream_t s) {
+  unsigned blocks = 0;
+  if (const int st = set_tiles(a, ti, tj, tk, &blocks)) return st;
+  if (const int st = reserve_lds(kernel, lds)) return st;
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(tj * tk), lds, s, a, (ti == 16 && tj == 16 && tk == 16) ? plan : static_cast<const int*>(nullptr));
   return check_launch("tio_resample3d");
 }
 
+// F32_ONLY: an experimental shape (TIO_TILE_VARIANT), built for float32 launches only — others take the default shape
+template <int TI, int TJ, int TK, int OCC, bool F32_ONLY>
+int launch_brick_shape(ResampleArgs& a, int dtmode, size_t lds, const int* plan, hipStream_t s) {
+  if constexpr (F32_ONLY) {
+    if (dtmode != 0) return launch_brick_shape<16, 16, 16, 3, false>(a, dtmode, lds, plan, s);
+  }
+  const BrickKernel kernel = with_bools([&](auto elastic) -> BrickKernel {
+    if constexpr (!F32_ONLY) {
+      if (dtmode == 1) return resample_tile_kernel<elastic.value, 1, TI, TJ, TK, OCC>;
+      if (dtmode != 0) return resample_tile_kernel<elastic.value, 2, TI, TJ, TK, OCC>;
+    }
+    return resample_tile_kernel<elastic.value, 0, TI, TJ, TK, OCC>;
+  }, a.cp != nullptr);
+  return launch_brick_kernel(kernel, TI, TJ, TK, a, lds, plan, s);
+}
+
+// brick, planned brick and FAST brick: resample_tile_kernel
+int launch_brick(const tio_resample_geom* geom, ResampleArgs& a, const FloatRoad& r, int dtmode, hipStream_t s) {
+  if (r.kind == kRoadFastBrick) {
+    const BrickKernel kernel = with_bools([](auto elastic) -> BrickKernel { return resample_tile_kernel<elastic.value, 0, 16, 16, 16, 3, true>; }, a.cp != nullptr);
+    return launch_brick_kernel(kernel, 16, 16, 16, a, r.lds, nullptr, s);
+  }
+  Plan plan;  // (a lease is held until the brick kernel is enqueued)
+  if (r.kind == kRoadPlannedBrick) {
+    int n_items = 0;
+    if (const int st = plan_bricks(geom, a, r.plan_need, s, &plan, &n_items)) return st;
+  }
+  switch (r.variant) {
+    case 1: return launch_brick_shape<16, 8, 32, 3, true>(a, dtmode, r.lds, plan.ptr, s);
+    case 2: return launch_brick_shape<8, 8, 32, 4, true>(a, dtmode, r.lds, plan.ptr, s);
+    case 3: return launch_brick_shape<8, 16, 32, 2, true>(a, dtmode, r.lds, plan.ptr, s);  // 512 threads, 2 blocks per CU
+    case 4: return launch_brick_shape<8, 16, 16, 4, true>(a, dtmode, r.lds, plan.ptr, s);
+    default: return launch_brick_shape<16, 16, 16, 3, false>(a, dtmode, r.lds, plan.ptr, s);
+  }
+}
+
+// planned FAST (TIO_PLANNED_LEAN=0): one launch of resample_planned_kernel for all images and channels
+int launch_planned_fast(const tio_resample_geom* geom, ResampleArgs& a, const FloatRoad& r, bool may_fold, hipStream_t s, bool* folded) {
+  Plan plan;
+  int n_items = 0;
+  if (const int st = plan_bricks(geom, a, r.plan_need, s, &plan, &n_items)) return st;
+  FoldedMin fm;
+  if (const int st = take_folded_min(a, may_fold, s, &fm)) return st;
+  *folded = fm.channels > 0;
+  const BrickKernel kernel = with_bools([](auto elastic) -> BrickKernel { return resample_planned_kernel<elastic.value, 16, 16, 16, 3>; }, a.cp != nullptr);
+  if (const int st = reserve_lds(kernel, r.lds)) return st;
+  hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(n_items)), dim3(256), r.lds, s, a, static_cast<const int*>(plan.ptr));
+  finish_folded_min(fm, s);
+  return check_launch("tio_resample3d");
+}
+
+// la.in / out / fill / strides (SECOND: the pair kernels' second channel) for channel c of image g
+template <bool SECOND>
+void set_lean_channel(LeanArgs& la, const ImgArgs& g, int c) {
+  const int64_t n_in = static_cast<int64_t>(la.I) * la.J * la.K, n_out = static_cast<int64_t>(la.Io) * la.Jo * la.Ko;
+  const float *in = static_cast<const float*>(g.in) + c * n_in, *fill = g.fill != nullptr ? g.fill + c : nullptr;
+  float* out = static_cast<float*>(g.out) + c * n_out;
+  const int64_t in_stride = g.channels * n_in, out_stride = g.channels * n_out;
+  if constexpr (SECOND) { la.in2 = in; la.out2 = out; la.fill2 = fill; la.in_stride2 = in_stride; la.out_stride2 = out_stride; }
+  else { la.in = in; la.out = out; la.fill = fill; la.in_stride = in_stride; la.out_stride = out_stride; }
+}
+
+// Planned lean (FAST coordinates) and lean exact (the reference's): one plan, one launch per channel of every image.  Lean exact without multi-pass bricks and without a
+// folded minimum samples two channels per launch (resample_lean_exact_pair_kernel: one descriptor round trip, one set of control planes, ONE coordinate chain for both —
+// a subject's float32 images share their geometry; an odd channel out goes alone) and takes the call's pending label channel along with the last of them
+// (resample_lean_exact_label_kernel).  TIO_LEAN_PAIR=0: one launch per channel, TIO_LEAN_LABEL=0: the label map's own kernel (A/B)
+int launch_lean(const tio_resample_geom* geom, ResampleArgs& a, const FloatRoad& r, bool may_fold, const NearestArgs& nn, LabelRide* label, hipStream_t s, bool* folded) {
+  Plan plan;  // (a lease is held until the last launch is enqueued)
+  int n_items = 0, channels = 0;
+  if (const int st = plan_bricks(geom, a, r.plan_need, s, &plan, &n_items)) return st;
+  FoldedMin fm;
+  if (const int st = take_folded_min(a, may_fold, s, &fm)) return st;
+  *folded = fm.channels > 0;
+  const bool elastic = a.cp != nullptr, lean_exact = r.kind == kRoadLeanExact, fold = fm.channels > 0;
+  const dim3 grid(static_cast<unsigned>(n_items)), grid_multi(static_cast<unsigned>(std::min<int64_t>(n_items, 3 * 256))), block(256);
+  LeanArgs la = make_lean_args(a, r, plan.ptr, n_items);
+  for (int i = 0; i < a.n_images; i++) channels += a.img[i].channels;
+  LeanKernel kernel;
+  if (lean_exact && a.plan_multi == 2)  // most bricks need passes: ONE launch of the body that knows them
+    kernel = with_bools([](auto e, auto x, auto f) -> LeanKernel { return resample_lean_exact_all_kernel<e.value, x.value, f.value>; }, elastic, r.exact_lerp, fold);
+  else if (lean_exact)
+    kernel = with_bools([](auto e, auto x, auto f) -> LeanKernel { return resample_lean_exact_kernel<e.value, x.value, 3, f.value>; }, elastic, r.exact_lerp, fold);
+  else if (a.ablate != 0)  // TIO_TILE_ABLATE: the instrumented instantiation (experiments only)
+    kernel = with_bools([](auto e) -> LeanKernel { return resample_planned_lean_kernel<e.value, 16, 16, 16, 3, true>; }, elastic);
+  else  // (the folded minimum: the instantiation whose element-0 bricks track what they store)
+    kernel = with_bools([](auto e, auto f) -> LeanKernel { return resample_planned_lean_kernel<e.value, 16, 16, 16, 3, false, f.value>; }, elastic, fold);
+  if (const int st = reserve_lds(kernel, r.lds)) return st;
+  // plan_multi == 1: behind every launch, the kernel whose blocks walk the planner's list of multi-pass bricks — three per CU, leaving at once when the list is empty
+  LeanKernel kernel_multi = nullptr, kernel_pair = nullptr, kernel_label_pair = nullptr, kernel_label_one = nullptr;
+  if (a.plan_multi == 1) {
+    kernel_multi = with_bools([](auto e, auto x, auto f) -> LeanKernel { return resample_lean_exact_multi_kernel<e.value, x.value, f.value>; }, elastic, r.exact_lerp, fold);
+    if (const int st = reserve_lds(kernel_multi, r.lds)) return st;
+  }
+  const bool plain = lean_exact && a.plan_multi == 0 && !fold;
+  const bool pairs = plain && channels >= 2 && r.pair != 0, label_here = plain && label->es != 0 && a.passthrough == nn.passthrough;
+  if (pairs || label_here) {
+    kernel_pair = with_bools([](auto e, auto x) -> LeanKernel { return resample_lean_exact_pair_kernel<e.value, x.value>; }, elastic, r.exact_lerp);
+    if (const int st = reserve_lds(kernel_pair, r.lds)) return st;
+  }
+  if (label_here) {
+    kernel_label_pair = with_bools([](auto e, auto x) -> LeanKernel { return resample_lean_exact_label_kernel<e.value, x.value, true>; }, elastic, r.exact_lerp);
+    kernel_label_one = with_bools([](auto e, auto x) -> LeanKernel { return resample_lean_exact_label_kernel<e.value, x.value, false>; }, elastic, r.exact_lerp);
+    if (const int st = reserve_lds(kernel_label_pair, r.lds)) return st;
+    if (const int st = reserve_lds(kernel_label_one, r.lds)) return st;
+    la.lab_in = nn.img[0].in; la.lab_out = nn.img[0].out; la.lab_es = label->es;
+  }
+  int launches_left = channels;
+  bool have_first = false;
+  for (int i = 0; i < a.n_images; i++) {
+    const ImgArgs& g = a.img[i];
+    for (int c = 0; c < g.channels; c++) {
+      --launches_left;
+      if (pairs && !have_first && launches_left > 0) {  // the first of two (an odd channel out is launched alone, below)
+        set_lean_channel<false>(la, g, c);
+        have_first = true;
+        continue;
+      }
+      la.last_use = !plan.made_ahead && launches_left == 0;  // (only the leased workspace is left zeroed, and only by the call's last launch)
+      la.min_keys = (fold && g.min_keys != nullptr) ? g.min_keys + c * kMinSlots : nullptr;
+      const bool with_label = label_here && launches_left == 0;
+      if (have_first) set_lean_channel<true>(la, g, c);
+      else set_lean_channel<false>(la, g, c);
+      const LeanKernel launch = have_first ? (with_label ? kernel_label_pair : kernel_pair) : (with_label ? kernel_label_one : kernel);
+      have_first = false;
+      hipLaunchKernelGGL(launch, grid, block, r.lds, s, la);
+      if (kernel_multi != nullptr) hipLaunchKernelGGL(kernel_multi, grid_multi, block, r.lds, s, la);
+    }
+  }
+  finish_folded_min(fm, s);
+  if (label_here) label->es = 0;  // (taken along)
+  return check_launch("tio_resample3d");
+}
+
+// `folded` comes back true when the launch itself produced every requested out_min_dev (planned FAST / lean bricks)
+int resample3d_impl(const tio_resample_geom* geom, int32_t n_images, const tio_resample_image* images, void* stream, bool* folded) {
+  *folded = false;
+  if (geom == nullptr || images == nullptr) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_resample3d: null argument");
+  if (n_images < 1 || n_images > TIO_MAX_IMAGES)
+    return fail(TIO_ERR_INVALID_ARGUMENT, "tio_resample3d: n_images=%d not in [1, %d]", n_images, TIO_MAX_IMAGES);
+  ResampleArgs a{};
+  int status = check_geometry(geom, a);
+  if (status != TIO_OK || a.B == 0) return status;
+  ResampleArgs pv = a, spl = a;
+  pv.any_linear = 1;
+  NearestArgs nn = make_nearest_args(a);
+  FloatGroup group;
+  const EnvSwitches& env = env_switches();  // (parsed once per process / tio_reload_env(): no getenv on this road)
+  if ((status = sort_images(n_images, images, env, a, pv, spl, nn, group)) != TIO_OK) return status;
+
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  LabelRide label;
+  if (nn.n_images > 0) {
+    const bool floats_alone = a.n_images > 0 && pv.n_images == 0 && spl.n_images == 0 && !group.any_adjoint;
+    if ((status = launch_nearest(nn, a.short_div != 0, floats_alone, env, s, &label)) != TIO_OK) return status;
+    if (a.n_images == 0 && pv.n_images == 0 && spl.n_images == 0) return check_launch("tio_resample3d");
+  }
+  if (pv.n_images > 0) {
+    if ((status = launch_label_pv(pv, s)) != TIO_OK) return status;
+    if (a.n_images == 0 && spl.n_images == 0) return check_launch("tio_resample3d");
+  }
+  if (spl.n_images > 0) {
+    if ((status = launch_bspline(spl, s)) != TIO_OK) return status;
+    if (a.n_images == 0) return check_launch("tio_resample3d");
+  }
+
+  const FloatRoad road = choose_float_road(*geom, a, group, env);
+  apply_road(a, road);
+  switch (road.kind) {
+    case kRoadGather: status = launch_gather(a, group.dtmode, s); break;
+    case kRoadBrick: case kRoadPlannedBrick: case kRoadFastBrick: status = launch_brick(geom, a, road, group.dtmode, s); break;
+    case kRoadPlannedFast: status = launch_planned_fast(geom, a, road, pv.n_images == 0, s, folded); break;
+    case kRoadPlannedLean: case kRoadLeanExact: status = launch_lean(geom, a, road, pv.n_images == 0, nn, &label, s, folded); break;
+  }
+  // a label channel nobody took along: its own launch, behind the float images' kernels — also where their road failed
+  // (the images' status is already decided: a failure of this launch is not reported)
+  if (label.es != 0) launch_nearest_exact(nn, label.es, label.blocks, label.lds, s);
+  return status;
+}
+
+// the plan entry points choose for one float32 trilinear image whose rows are 16-byte aligned (the planner never reads an image)
+int choose_plan_road(const tio_resample_geom* geom, ResampleArgs* a, FloatRoad* road) {
+  const int status = check_geometry(geom, *a);
+  if (status != TIO_OK) return status;
+  a->any_linear = 1;
+  *road = choose_float_road(*geom, *a, FloatGroup{}, env_switches());
+  return TIO_OK;
+}
+
+}  // namespace
+
 extern "C" int64_t tio_resample3d_plan_bytes(const tio_resample_geom* geom) {
-  bool folded = false;
-  int64_t bytes = 0;
   if (geom == nullptr || geom->batch < 1) return 0;
-  const int status = resample3d_impl(geom, 0, nullptr, nullptr, &folded, kPlanQuery, nullptr, 0, &bytes);
-  return status == TIO_OK ? bytes : 0;
+  ResampleArgs a{};
+  FloatRoad road;
+  return choose_plan_road(geom, &a, &road) == TIO_OK ? static_cast<int64_t>(road.plan_need) : 0;
 }
 
 extern "C" int tio_resample3d_plan(const tio_resample_geom* geom, void* plan_dev, int64_t plan_bytes, void* stream) {
-  bool folded = false;
-  int64_t bytes = 0;
   if (geom == nullptr || geom->batch < 1) return tio::fail(TIO_ERR_INVALID_ARGUMENT, "tio_resample3d_plan: no geometry / empty batch");
-  const int status = resample3d_impl(geom, 0, nullptr, stream, &folded, kPlanOnly, static_cast<int*>(plan_dev), plan_bytes, &bytes);
-  if (status == TIO_OK && bytes == 0) return tio::fail(TIO_ERR_INVALID_ARGUMENT, "tio_resample3d_plan: this geometry's launch does not start from a plan");
-  return status;
+  ResampleArgs a{};
+  FloatRoad road;
+  if (const int st = choose_plan_road(geom, &a, &road)) return st;
+  if (road.plan_need == 0) return tio::fail(TIO_ERR_INVALID_ARGUMENT, "tio_resample3d_plan: this geometry's launch does not start from a plan");
+  if (plan_dev == nullptr || plan_bytes < static_cast<int64_t>(road.plan_need) || (reinterpret_cast<uintptr_t>(plan_dev) & 15) != 0)
+    return tio::fail(TIO_ERR_INVALID_ARGUMENT, "tio_resample3d_plan: the plan needs %zu bytes, 16-byte aligned", road.plan_need);
+  apply_road(a, road);
+  unsigned bricks = 0;
+  if (const int st = set_tiles(a, 16, 16, 16, &bricks)) return st;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // The header of the multi-pass bricks' list (length, cursor, done count) is zero between launches: the leased workspace is zeroed when it is allocated and the last
+  // walker of a call's last launch leaves zeros (la.last_use); a caller's buffer is zeroed here and keeps its length after every call it is handed to (a plan made ahead
+  // serves any number of calls).  Only the lean exact road lists such bricks: the planned brick road has plan_multi == 0, nothing reads its header.
+  if (a.plan_multi && hipMemsetAsync(plan_dev, 0, kPlanHeaderInts * sizeof(int), s) != hipSuccess)
+    return tio::fail(TIO_ERR_LAUNCH, "tio_resample3d_plan: cannot reset the brick plan");
+  enqueue_planner(a, static_cast<int*>(plan_dev) + kPlanHeaderInts, static_cast<int>(bricks), s);
+  return tio::check_launch("tio_resample3d_plan");
 }
 
 extern "C" int tio_resample3d(const tio_resample_geom* geom, int32_t n_images, const tio_resample_image* images, void* stream) {
@@ -1359,4 +1358,3 @@ extern "C" int tio_resample3d(const tio_resample_geom* geom, int32_t n_images, c
   }
   return TIO_OK;
 }
-
