@@ -14,6 +14,9 @@
  *     which synchronises that one time; do not capture their first call into a graph);
  *   - tensors are dense row-major (B, C, I, J, K) — K fastest — exactly the
  *     layout of ImagesBatch.data (reference src/torchio/data/batch.py:21-50);
+ *   - alignment of the element type suffices for every pointer unless an entry point asks for more (plan_dev,
+ *     tio_blur_fused, noise_base_dev, tio_unique_labels: 16 bytes) — the 16-byte roads look at the pointers they are
+ *     given and leave the work to their element-wise twins, same values, when a dense view starts off such a boundary;
  *   - inputs are borrowed, outputs must not alias inputs;
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream);
  *   - every function returns TIO_OK (0) or a negative tio_status; the failing

@@ -14,29 +14,15 @@ import itertools
 import pytest
 import torch
 
+from case_inputs import _control_points  # noqa: F401 - other test modules import the builders from here
+from case_inputs import _data
+from case_inputs import _mapping
+from case_inputs import _segments
+from case_inputs import _taps
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-
-
-def _mapping(batch, seed, scale=0.15, shift=3.0):
-    g = torch.Generator().manual_seed(seed)
-    m = torch.eye(3, 4).repeat(batch, 1, 1)
-    m[:, :, :3] += scale * torch.randn(batch, 3, 3, generator=g)
-    m[:, :, 3] = shift * torch.randn(batch, 3, generator=g)
-    return m.float()
-
-
-def _control_points(batch, shape, seed, amplitude=4.0):
-    g = torch.Generator().manual_seed(seed)
-    return ((torch.rand(batch, *shape, 3, generator=g) - 0.5) * 2 * amplitude).float()
-
-
-def _data(shape, dtype, seed):
-    g = torch.Generator().manual_seed(seed)
-    if dtype.is_floating_point:
-        return (torch.rand(*shape, generator=g) * 4 - 1).to(dtype)
-    return torch.randint(0, 7, shape, generator=g).to(dtype)
 
 
 def _both(oracle, hip, fn, tensors, **kwargs):
@@ -164,32 +150,6 @@ def test_channel_min(oracle, hip):
         cpu, gpu = _both(oracle, hip, "channel_min", (data,))
         assert torch.equal(cpu, gpu.cpu())
         assert torch.equal(cpu, data[0].float().amin(dim=(1, 2, 3)))
-
-
-def _taps(batch, sigmas, stride):
-    taps = torch.zeros(batch, 3, stride)
-    radius = [0, 0, 0]
-    for b in range(batch):
-        for axis in range(3):
-            s = sigmas[b][axis]
-            if s <= 0:
-                continue
-            r = max(int(-(-3 * s // 1)), 1)
-            radius[axis] = max(radius[axis], r)
-    for b in range(batch):
-        for axis in range(3):
-            r = radius[axis]
-            if r == 0:
-                continue
-            s = sigmas[b][axis]
-            x = torch.arange(2 * r + 1, dtype=torch.float32) - r
-            if s > 0:
-                k = torch.exp(-0.5 * (x / s) ** 2)
-                k[(x.abs() > max(int(-(-3 * s // 1)), 1))] = 0
-            else:
-                k = (x == 0).float()
-            taps[b, axis, : 2 * r + 1] = k / k.sum()
-    return taps, radius
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float16, torch.float64, torch.bfloat16])
@@ -449,11 +409,6 @@ def test_pad3d_per_element_constants_and_limits(oracle, hip):
     with pytest.raises(EngineError, match="paddings >= 0"):
         hip.pad3d(data.to(DEV), (0, 0, 0, -1, 0, 0))
     assert hip.pad3d(data[:0].to(DEV), (1, 1, 1, 1, 1, 1)).shape == (0, 2, 7, 8, 9)
-
-
-def _segments(shape, n, seed):
-    g = torch.Generator().manual_seed(seed)
-    return [(torch.rand(*shape, generator=g) * 4 - 1) for _ in range(n)]
 
 
 @pytest.mark.parametrize(

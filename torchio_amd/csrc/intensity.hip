@@ -920,8 +920,11 @@ static int launch_conv(const void* x, void* y, float* tmp0, float* tmp1, int32_t
   const void* src = x;
   // J and K can share one pass when the whole K row sits in one 256-wide tile and both radii
   // are small: the J kernel filters every row it produces along K before storing it
+  // (only the 16-byte kernels have the fused K stage: with a pointer that keeps a pass off them — the gate of the loop
+  // below — the K pass must stay in the plan, or nothing filters along K)
   const bool fuse_jk = DT == TIO_F32 && radius[1] > 0 && radius[2] > 0 && radius[1] <= kConvMaxRadiusV4 && radius[2] <= 8 &&
-                       shape[2] <= 256 && (shape[2] & 3) == 0 && !env_switches().conv_no_fuse;
+                       shape[2] <= 256 && (shape[2] & 3) == 0 && !env_switches().conv_no_fuse &&
+                       ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(tmp0)) & 15) == 0;
   if (fuse.any()) {
     // the pointwise stages ride on the marching I pass (loads) and the fused J+K pass (stores)
     const bool ok = DT == TIO_F32 && n_active == 3 && fuse_jk && radius[0] <= kConvMaxRadiusV4 && skip == nullptr &&
@@ -1158,7 +1161,8 @@ __global__ __launch_bounds__(kBlock) void philox_normal_kernel(float* __restrict
   if (4 * q >= n) return;
   float z[4];
   philox_normal4(seed, stream_id, static_cast<uint64_t>(q), z);
-  if (4 * q + 3 < n) {
+  // (one 16-byte store where `out` allows it: a caller's dense view may start anywhere on an element boundary)
+  if (4 * q + 3 < n && (reinterpret_cast<uintptr_t>(out) & 15) == 0) {
     *reinterpret_cast<float4*>(out + 4 * q) = make_float4(z[0], z[1], z[2], z[3]);
   } else {
     for (int t = 0; t < 4; t++)
@@ -1578,6 +1582,8 @@ extern "C" int tio_blur_fused(const void* x, void* y, void* tmp, int32_t dtype, 
   if (noise_on < 0 || noise_on > 2) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_blur_fused: noise_on must be 0, 1 or 2");
   if (noise_on == 2 && noise_base_dev == nullptr) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_blur_fused: noise_on == 2 needs noise_base_dev");
   if (noise_on == 2 && (reinterpret_cast<uintptr_t>(noise_base_dev) & 15) != 0) return TIO_ERR_UNSUPPORTED_CONFIG;
+  // (the header's contract, with or without a stage riding along: launch_conv itself asks only when one does)
+  if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(tmp)) & 15) != 0) return TIO_ERR_UNSUPPORTED_CONFIG;
   if (batch == 0) return TIO_OK;
   const int64_t n = static_cast<int64_t>(shape[0]) * shape[1] * shape[2];
   ConvFuse fuse;

@@ -313,7 +313,11 @@ extern "C" int tio_kspace_segment_mix(const void* const* segments, int32_t n_seg
   }
   a.mix = mix_dev; a.out = out; a.active = active_dev;
   a.n_seg = n_segments; a.I = shape[0]; a.N = static_cast<int>(n); a.dtype = dtype; a.channels = channels;
-  const bool aligned = (shape[0] % 4 == 0) && (n % 4 == 0);
+  // the ALIGNED instantiation loads float4 from every segment and from the table: the shape makes every such offset a
+  // multiple of four elements, the base pointers have to be 16-byte aligned as well (a dense view that starts one
+  // element into a buffer is not) - otherwise the element-wise instantiation, which computes the same values
+  bool aligned = (shape[0] % 4 == 0) && (n % 4 == 0) && reinterpret_cast<uintptr_t>(mix_dev) % 16 == 0;
+  for (int s = 0; s < n_segments; s++) aligned = aligned && reinterpret_cast<uintptr_t>(segments[s]) % 16 == 0;
   const int rm = shape[0] > 128 ? 2 : 1, bm = 128 * rm;
   dim3 grid(static_cast<unsigned>((n + kBN - 1) / kBN), static_cast<unsigned>((shape[0] + bm - 1) / bm), static_cast<unsigned>(bc));
   hipStream_t s = static_cast<hipStream_t>(stream);
