@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define TIO_ABI_VERSION 16
+#define TIO_ABI_VERSION 17
 #define TIO_MAX_IMAGES 8 /* images resampled per launch with shared coordinates */
 
 typedef enum tio_status {
@@ -503,6 +503,70 @@ int tio_patch_accumulate(void* out, void* weight_sum, int32_t dtype, int32_t cha
  */
 int tio_unique_labels(const void* x, int32_t dtype, int64_t n, double* table_dev, int32_t* count_dev,
                       void* workspace_dev, void* stream);
+
+/* ------------------------------------------------------------------------ */
+/* Label-map transforms (ABI 17)                                             */
+/* ------------------------------------------------------------------------ */
+
+typedef enum tio_remap_mode {
+  TIO_REMAP_KEEP = 0,    /* a value that is no key stays                      (remap_labels.py:54, remove_labels.py:57) */
+  TIO_REMAP_CONSTANT = 1 /* a value that is no key becomes `constant`         (sequential_labels.py:58: zeros_like)     */
+} tio_remap_mode;
+#define TIO_REMAP_MAX_PAIRS 65536
+
+/*
+ * RemapLabels / RemoveLabels / SequentialLabels and its inverse (remap_labels.py:54-57, remove_labels.py:57-60,
+ * sequential_labels.py:58-61, :100-104: one full-volume `data == old` plus a masked write PER PAIR) as one pass for any
+ * number of pairs: y[v] = values[j] where double(x[v]) == keys[j], else x[v] (KEEP) or `constant` (CONSTANT), both cast
+ * to the dtype.  Every comparison is against the ORIGINAL value, so {1: 2, 2: 1} swaps, as in the reference.
+ *   x, y        n elements of any tio_dtype; y == x (in place) is allowed
+ *   keys_dev    device, n_pairs <= TIO_REMAP_MAX_PAIRS doubles, strictly ASCENDING (unique)
+ *   values_dev  device, n_pairs doubles
+ *   table_dev   device scratch of 65536 int16 (128 KiB), TIO_I16 only (NULL otherwise): the dense table a one-block launch
+ *               fills in front of the streaming one.  8-bit data: a 256-entry table in LDS; every other dtype: a binary
+ *               search in the keys (from LDS up to 2048 pairs).
+ */
+int tio_label_remap(const void* x, void* y, int32_t dtype, int64_t n, const double* keys_dev,
+                    const double* values_dev, int32_t n_pairs, int32_t mode, double constant,
+                    void* table_dev, void* stream);
+
+/*
+ * OneHot (one_hot.py:64-68: .long(), F.one_hot, permute, .float()): x is (B, 1, n_spatial) of any tio_dtype, y is
+ * (B, num_classes, n_spatial) float32 with y[b, c, v] = (x[b, 0, v] == c).  The input is read once.
+ *   status_dev  device, one int32, cleared by the call: non-zero afterwards when some value was negative, >= num_classes
+ *               or no integer (F.one_hot raises there; such a voxel is 0 in every class here and the caller raises).
+ */
+int tio_label_one_hot(const void* x, float* y, int32_t dtype, int32_t batch, int64_t n_spatial,
+                      int32_t num_classes, int32_t* status_dev, void* stream);
+
+/*
+ * Contour (contour.py:66-70: F.pad(value=-1), -max_pool3d(-padded, 3), `eroded != data.float()`): for every one of the
+ * n_batch_channels volumes, y = (min over the 3 x 3 x 3 neighbourhood of float32(x), -1 outside the volume) != float32(x)
+ * as float32 0 / 1.  What the code computes, not its docstring: the 26-neighbourhood, a voxel is marked where a neighbour
+ * is SMALLER, and every voxel on a face of the volume is marked unless its value is <= -1.
+ */
+int tio_label_contour(const void* x, float* y, int32_t dtype, int64_t n_batch_channels,
+                      const int32_t shape[3], void* stream);
+
+#define TIO_KEEP_LARGEST_MAX_LABELS 1024 /* labels per call (the caller splits a longer list) */
+
+/*
+ * KeepLargestComponent (keep_largest.py:108-125: per label and batch element a mask copied to the HOST, SimpleITK's
+ * ConnectedComponent + RelabelComponent, a masked write).  x, y: (B, 1, I, J, K) of TIO_U8 / I8 / I16 / I32 / I64 / F32
+ * (others: TIO_ERR_UNSUPPORTED_DTYPE), y must not alias x.  y = x, except that a voxel whose value is listed and whose
+ * connected component — of voxels of that same value, inside its batch element, 26-connected when fully_connected else
+ * 6-connected — is not the largest such component of that value in that element becomes `background`.  All listed labels
+ * are handled in one pass.  Of equally large components the one whose first voxel comes first in C order is kept.
+ *   labels_dev     device, n_labels <= TIO_KEEP_LARGEST_MAX_LABELS doubles, strictly ascending
+ *                  (more: TIO_ERR_UNSUPPORTED_CONFIG)
+ *   workspace_dev  device, 16-byte aligned, workspace_bytes >= the size the helper below returns for these arguments
+ * B * I * J * K >= 2^31: TIO_ERR_UNSUPPORTED_CONFIG (voxel indices are int32).
+ */
+int64_t tio_keep_largest_workspace_bytes(int32_t batch, const int32_t shape[3], int32_t n_labels);
+int tio_keep_largest_component(const void* x, void* y, int32_t dtype, int32_t batch, const int32_t shape[3],
+                               const double* labels_dev, int32_t n_labels, double background,
+                               int32_t fully_connected, void* workspace_dev, int64_t workspace_bytes,
+                               void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* Motion: k-space compositing                                               */

@@ -46,6 +46,12 @@ from .transforms import ElasticDeformation
 from .transforms import Flip
 from .transforms import Gamma
 from .transforms import IntensityTransform
+from .transforms import Contour
+from .transforms import KeepLargestComponent
+from .transforms import OneHot
+from .transforms import RemapLabels
+from .transforms import RemoveLabels
+from .transforms import SequentialLabels
 from .transforms import Motion
 from .transforms import Noise
 from .transforms import OneOf
@@ -63,8 +69,8 @@ from .transforms import set_noise_rng
 __version__ = "0.1.0"
 
 __all__ = [
-    "Affine", "AffineMatrix", "Anisotropy", "AppliedTransform", "BiasField", "Blur", "Choice", "Compose", "Crop", "ElasticDeformation", "Flip",
-    "Gamma", "GridSampler", "Image", "ImagesBatch", "ImagesLoader", "IntensityTransform", "LabelMap", "LabelSampler", "Motion", "Noise", "OneOf",
-    "Pad", "PatchAggregator", "PatchLocation", "PatchSampler", "Queue", "Resample", "Resize", "ScalarImage", "SomeOf", "Spatial", "SpatialTransform", "Subject",
+    "Affine", "AffineMatrix", "Anisotropy", "AppliedTransform", "BiasField", "Blur", "Choice", "Compose", "Contour", "Crop", "ElasticDeformation", "Flip",
+    "Gamma", "GridSampler", "Image", "ImagesBatch", "ImagesLoader", "IntensityTransform", "KeepLargestComponent", "LabelMap", "LabelSampler", "Motion", "Noise", "OneHot", "OneOf",
+    "Pad", "PatchAggregator", "PatchLocation", "PatchSampler", "Queue", "RemapLabels", "RemoveLabels", "Resample", "Resize", "ScalarImage", "SequentialLabels", "SomeOf", "Spatial", "SpatialTransform", "Subject",
     "SubjectsBatch", "SubjectsLoader", "Transform", "UniformSampler", "WeightedSampler", "apply_inverse_transform", "calibrate_draw_policy", "get_draw_policy", "set_draw_policy", "get_noise_plan", "set_noise_plan", "get_inverse_transform", "get_noise_rng", "get_resample_precision", "get_stencil_precision", "set_noise_rng", "set_resample_precision", "set_stencil_precision",
 ]

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 MAX_IMAGES = 8
 
 # tio_status
@@ -22,6 +22,10 @@ NEAREST, LINEAR, LABEL_PV, LINEAR_ADJOINT, QUADRATIC, CUBIC = 0, 1, 2, 3, 4, 5
 BSPLINE4, BSPLINE5, BSPLINE6, BSPLINE7 = 6, 7, 8, 9  # B-spline orders 4 - 7 ("fourth" ... "seventh")
 # tio_pad_mode
 PAD_CONSTANT, PAD_REFLECT, PAD_REPLICATE, PAD_CIRCULAR = 0, 1, 2, 3
+# tio_remap_mode
+REMAP_KEEP, REMAP_CONSTANT = 0, 1
+REMAP_MAX_PAIRS = 65536
+KEEP_LARGEST_MAX_LABELS = 1024
 # tio_precision
 PRECISION_EXACT, PRECISION_FAST, PRECISION_TIGHT = 0, 1, 2
 GEOM_LARGE_BOXES = 1  # tio_resample_geom.flags (ABI 14): SOME bricks' boxes exceed the staging tile
@@ -169,6 +173,19 @@ HIP_ONLY_PROTOTYPES = {
         [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _I32x3, C.c_void_p, C.c_int32, C.c_int32,
          _I32x3, C.c_void_p, _I32x3, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64,
          C.c_void_p, C.c_int32, C.c_void_p],
+    ),
+    # the label-map transforms (ABI 17): no CPU restatement in the oracle
+    "label_remap": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p],
+    ),
+    "label_one_hot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "label_contour": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, _I32x3, C.c_void_p]),
+    "keep_largest_workspace_bytes": (C.c_int64, [C.c_int32, _I32x3, C.c_int32]),
+    "keep_largest_component": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _I32x3, C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_int64,
+         C.c_void_p],
     ),
 }
 

@@ -1529,6 +1529,103 @@ class Engine:
                    self._stream(data))
         return table[: int(count.item())]
 
+    # -- label-map transforms (transforms/label/*.py of the reference) ---------------------------------------------------
+    def label_remap(self, data: Tensor, mapping, *, default: float | None = None, inplace: bool = False) -> Tensor:
+        """``out[v] = mapping[data[v]]`` for every pair at once, compared against the ORIGINAL values (``{1: 2, 2: 1}`` swaps).
+
+        A value that is no key stays (``default=None``) or becomes ``default``.  ``mapping``: a dict or a sequence of
+        ``(old, new)`` pairs with unique keys (at most 65536).  ``inplace=True`` writes into ``data`` (which must be dense).
+        """
+        pairs = sorted((float(old), float(new)) for old, new in (mapping.items() if hasattr(mapping, "items") else mapping))
+        if len({old for old, _ in pairs}) != len(pairs):
+            raise ValueError("label_remap: the keys of the mapping must be unique")
+        if len(pairs) > _abi.REMAP_MAX_PAIRS:
+            raise ValueError(f"label_remap: at most {_abi.REMAP_MAX_PAIRS} pairs, got {len(pairs)}")
+        if inplace and not data.is_contiguous():
+            raise ValueError("label_remap: inplace needs a contiguous tensor")
+        data = data.contiguous()
+        table = None
+        if pairs:
+            table = h2d(torch.tensor(pairs, dtype=torch.float64).t().contiguous(), data.device)  # row 0: keys, row 1: values
+        self._check("label_remap", data, table)
+        out = data if inplace else torch.empty_like(data)
+        scratch = torch.empty(65536, dtype=torch.int16, device=data.device) if data.dtype == torch.int16 else None
+        mode = _abi.REMAP_KEEP if default is None else _abi.REMAP_CONSTANT
+        self._call("label_remap", data, _ptr(data), _ptr(out), dtype_code(data.dtype), data.numel(),
+                   None if table is None else C.c_void_p(table[0].data_ptr()), None if table is None else C.c_void_p(table[1].data_ptr()),
+                   len(pairs), mode, 0.0 if default is None else float(default), _ptr(scratch), self._stream(data))
+        return out
+
+    def label_one_hot(self, data: Tensor, num_classes: int = -1) -> Tensor:
+        """``F.one_hot(data[:, 0].long(), num_classes)`` as float32 ``(B, num_classes, I, J, K)``; ``-1``: ``max + 1``.
+
+        One 4-byte read-back (the status word; ``F.one_hot`` synchronises for the same check), one more to infer the classes.
+        """
+        if data.ndim != 5 or data.shape[1] != 1:
+            raise ValueError(f"expected a (B, 1, I, J, K) label map, got {tuple(data.shape)}")
+        data = data.contiguous()
+        self._check("label_one_hot", data)
+        num_classes = int(num_classes)
+        if num_classes < 0:
+            if data.numel() == 0:
+                raise RuntimeError("Can not infer total number of classes from empty tensor.")
+            num_classes = int(data.max().item()) + 1
+            if num_classes <= 0:
+                raise RuntimeError("Class values must be non-negative.")
+        out = torch.empty((data.shape[0], num_classes, *data.shape[2:]), dtype=torch.float32, device=data.device)
+        status = torch.empty(1, dtype=torch.int32, device=data.device)
+        spatial = data.shape[2] * data.shape[3] * data.shape[4]
+        self._call("label_one_hot", data, _ptr(data), _ptr(out), dtype_code(data.dtype), data.shape[0], spatial, num_classes, _ptr(status),
+                   self._stream(data))
+        if data.numel() and int(status.item()) != 0:
+            raise RuntimeError(f"label_one_hot: class values must be integers in [0, {num_classes})")
+        return out
+
+    def label_contour(self, data: Tensor) -> Tensor:
+        """The reference's ``_extract_contour``: float32 1 where the 27-point minimum (-1 outside the volume) differs from the voxel."""
+        if data.ndim != 5:
+            raise ValueError(f"expected a (B, C, I, J, K) tensor, got {tuple(data.shape)}")
+        data = data.contiguous()
+        self._check("label_contour", data)
+        out = torch.empty(data.shape, dtype=torch.float32, device=data.device)
+        self._call("label_contour", data, _ptr(data), _ptr(out), dtype_code(data.dtype), data.shape[0] * data.shape[1], _i32x3(data.shape[2:]),
+                   self._stream(data))
+        return out
+
+    def keep_largest_component(self, data: Tensor, labels, *, background: float = 0, fully_connected: bool = True) -> Tensor:
+        """Per batch element and listed label value, every connected component but the largest becomes ``background``.
+
+        ``labels``: numbers, or a float64 tensor on the data's device (sorted, unique — ``unique_labels``'s result).  All labels
+        of a call are handled by one pass; a list beyond the library's cap is split into several.
+        """
+        if data.ndim != 5:
+            raise ValueError(f"expected a (B, C, I, J, K) tensor, got {tuple(data.shape)}")
+        if data.shape[1] != 1:
+            raise RuntimeError(f"KeepLargestComponent requires single-channel label maps, got {data.shape[1]} channels")
+        data = data.contiguous()
+        if not isinstance(labels, Tensor):
+            values = sorted({float(v) for v in labels})
+            labels = h2d(torch.tensor(values, dtype=torch.float64), data.device) if values else None
+        elif labels.numel() == 0:
+            labels = None
+        else:
+            labels = labels.to(torch.float64).contiguous()
+        self._check("keep_largest_component", data, labels)
+        if labels is None:
+            return data.clone()
+        shape = _i32x3(data.shape[2:])
+        result = None
+        for begin in range(0, labels.numel(), _abi.KEEP_LARGEST_MAX_LABELS):
+            chunk = labels[begin : begin + _abi.KEEP_LARGEST_MAX_LABELS]
+            out = torch.empty_like(data)
+            nbytes = int(self._fn["keep_largest_workspace_bytes"](data.shape[0], shape, chunk.numel()))
+            workspace = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=data.device)
+            self._call("keep_largest_component", data, _ptr(data), _ptr(out), dtype_code(data.dtype), data.shape[0], shape, _ptr(chunk),
+                       chunk.numel(), float(background), int(bool(fully_connected)), _ptr(workspace), nbytes, self._stream(data))
+            # (every chunk works on the original data: a removed voxel never counts for a later chunk's label)
+            result = out if result is None else torch.where(out != data, out, result)
+        return result
+
     def kspace_segment_mix(self, segments: Sequence[Tensor], bounds: Sequence[int], out_dtype: torch.dtype,
                            active: Tensor | None = None) -> Tensor:
         """Motion's k-space composite (motion.py:334-372) of float32 ``(B, C, I, J, K)`` images.

@@ -8,6 +8,12 @@ from .flip import Flip
 from .gamma import Gamma
 from .inverse import apply_inverse_transform
 from .inverse import get_inverse_transform
+from .labels import Contour
+from .labels import KeepLargestComponent
+from .labels import OneHot
+from .labels import RemapLabels
+from .labels import RemoveLabels
+from .labels import SequentialLabels
 from .motion import Motion
 from .noise import Noise
 from .noise import get_noise_rng
@@ -26,7 +32,8 @@ from .transform import SpatialTransform
 from .transform import Transform
 
 __all__ = [
-    "Affine", "Anisotropy", "AppliedTransform", "BiasField", "Blur", "Choice", "Compose", "Crop", "ElasticDeformation", "Flip", "Gamma",
-    "IntensityTransform", "Motion", "Noise", "OneOf", "Pad", "Resample", "Resize", "SomeOf", "Spatial", "SpatialTransform", "Transform",
+    "Affine", "Anisotropy", "AppliedTransform", "BiasField", "Blur", "Choice", "Compose", "Contour", "Crop", "ElasticDeformation", "Flip", "Gamma",
+    "IntensityTransform", "KeepLargestComponent", "Motion", "Noise", "OneHot", "OneOf", "Pad", "RemapLabels", "RemoveLabels", "Resample", "Resize",
+    "SequentialLabels", "SomeOf", "Spatial", "SpatialTransform", "Transform",
     "apply_inverse_transform", "get_inverse_transform", "get_noise_rng", "set_noise_rng",
 ]
