@@ -569,6 +569,86 @@ int tio_keep_largest_component(const void* x, void* y, int32_t dtype, int32_t ba
                                void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* Intensity preprocessing with on-device statistics (ABI 17, additive)      */
+/* ------------------------------------------------------------------------ */
+/*
+ * Normalize / Standardize / Clamp / Mask (transforms/intensity/normalize.py, standardize.py, clamp.py, mask.py).  Every
+ * entry point reads every tio_dtype and converts an element to float32 first, as the reference's `.float()` does
+ * (float64 and int64 are rounded to float32).
+ *
+ * The two statistics read ONE batch element — `img_batch.data[0]`, (channels, n_spatial) — and an optional mask:
+ *   mask           device or NULL (every element counts), (mask_channels, n_spatial) of any tio_dtype (bool: TIO_U8);
+ *                  inside = nonzero (`.bool()`); mask_channels is 1 (broadcast over the channels) or `channels`
+ *   record_dev     device, 8-byte aligned, written by the call (layouts below)
+ *   workspace_dev  device, 16-byte aligned, at least tio_intensity_stats_workspace_bytes() bytes; it may hold anything
+ *                  (the kernels zero what they use) and may be reused by the next call on the same stream
+ */
+int64_t tio_intensity_stats_workspace_bytes(void);
+
+/*
+ * Standardize.make_params (standardize.py:63-76: a boolean gather, `.mean()`, `.std()`, two read-backs): the count, the
+ * mean and the unbiased standard deviation (n - 1) of the inside elements.  Accumulated in float64 (shifted sums per
+ * thread, Chan's pairwise merge above them), rounded ONCE to float32.  Per-block partials go to fixed slots and are merged
+ * in a fixed order, no float atomics: two calls on the same input return the same bits.
+ *   record_dev  { int64 count; float32 mean; float32 std; }  — count 0: mean and std NaN; count 1: std NaN (torch.std)
+ */
+int tio_intensity_moments(const void* x, int32_t dtype, int32_t channels, int64_t n_spatial, const void* mask,
+                          int32_t mask_dtype, int32_t mask_channels, void* record_dev, void* workspace_dev,
+                          int64_t workspace_bytes, void* stream);
+
+/*
+ * compute_quantile (transforms/_statistics.py:36-41: torch.kthvalue once or twice per quantile, each a selection pass
+ * with a read-back) for up to two fractions in one call.  With n the number of inside elements and
+ * lower = floor(q * (n - 1)) — float64, on the device, the reference's two operations — the record of fraction k holds
+ * the (lower + 1)-th and the (lower + 2)-th smallest inside value (the same value when lower == n - 1) and n; the host
+ * finishes with the reference's own `lower_value.lerp(upper_value, index - lower)`.  Exact: a radix select over an
+ * order-preserving 32-bit key (NaN sorts last, as torch.kthvalue sorts it; of -0 and +0 either may be returned) in three
+ * data passes of 11 / 11 / 10 bits, a one-block scan after each; no host round trip in between.
+ *   fractions    HOST, n_fractions (1 or 2) doubles in [0, 1]
+ *   record_dev   n_fractions x { float32 lower_value; float32 upper_value; int64 n; }  — n == 0: the values are NaN
+ */
+int tio_intensity_quantiles(const void* x, int32_t dtype, int32_t channels, int64_t n_spatial, const void* mask,
+                            int32_t mask_dtype, int32_t mask_channels, const double* fractions,
+                            int32_t n_fractions, void* record_dev, void* workspace_dev, int64_t workspace_bytes,
+                            void* stream);
+
+typedef enum tio_map_mode {
+  TIO_MAP_RESCALE_CLIP = 0, /* (min(max(x, in_min), in_max) - in_min) / in_range * out_range + out_min  (normalize.py:182-183) */
+  TIO_MAP_RESCALE = 1,      /* (x - out_min) / out_range * in_range + in_min: the inverse               (normalize.py:287, :297) */
+  TIO_MAP_SUB_DIV = 2,      /* (x - in_min) / in_range                                                  (standardize.py:97)     */
+  TIO_MAP_MUL_ADD = 3       /* x * in_range + in_min                                                    (standardize.py:138)    */
+} tio_map_mode;
+
+/*
+ * The elementwise half of Normalize, Standardize and their inverses in one pass: x is (batch, n_per_element) of any
+ * tio_dtype, y the same shape in float32.  Every operation is a separately rounded float32 operation — IEEE division, no
+ * multiply-add contraction — which is what ATen's CPU kernels compute for `(data - a) / b * c + d` with Python scalars.
+ * The clip propagates NaN like torch.clamp.
+ *   out_min_dev, out_range_dev  device, `batch` floats each, or both NULL (then the scalars out_min / out_range): the
+ *                  per-instance output range of _out_min_and_range (normalize.py:320-327); RESCALE modes only.  With
+ *                  them, RESCALE leaves an element whose out_range is 0 as it is (normalize.py:293-298).
+ */
+int tio_intensity_map(const void* x, float* y, int32_t dtype, int32_t batch, int64_t n_per_element, int32_t mode,
+                      float in_min, float in_max, float in_range, float out_min, float out_range,
+                      const float* out_min_dev, const float* out_range_dev, void* stream);
+
+/*
+ * Clamp (clamp.py:56: `data.clamp(min=, max=)` with Python floats; either bound optional, not both absent): NaN
+ * propagates.  y has torch's promoted dtype: the float dtypes stay (the bounds are cast to the dtype; float64 compares in
+ * float64), every integer dtype becomes float32.
+ */
+int tio_intensity_clamp(const void* x, void* y, int32_t dtype, int64_t n, int32_t has_min, double out_min,
+                        int32_t has_max, double out_max, void* stream);
+
+/*
+ * Mask (mask.py:69-70: `torch.where(mask.expand_as(data), data, outside_value)`): y[i] = x[i] where
+ * mask[i % mask_n] is nonzero, else outside_value; mask_n divides n (the mask of the first batch element, broadcast over
+ * the batch and, with one mask channel, over the channels).  y has the promoted dtype of tio_intensity_clamp.
+ */
+int tio_intensity_mask(const void* x, void* y, int32_t dtype, int64_t n, const void* mask, int32_t mask_dtype,
+                       int64_t mask_n, double outside_value, void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* Motion: k-space compositing                                               */
 /* ------------------------------------------------------------------------ */
 #define TIO_MAX_SEGMENTS 32

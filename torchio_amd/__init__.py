@@ -54,6 +54,12 @@ from .transforms import RemoveLabels
 from .transforms import SequentialLabels
 from .transforms import Motion
 from .transforms import Noise
+from .transforms import Clamp
+from .transforms import Mask
+from .transforms import Normalize
+from .transforms import RescaleIntensity
+from .transforms import Standardize
+from .transforms import ZNormalization
 from .transforms import OneOf
 from .transforms import SomeOf
 from .transforms import Resample
@@ -69,8 +75,8 @@ from .transforms import set_noise_rng
 __version__ = "0.1.0"
 
 __all__ = [
-    "Affine", "AffineMatrix", "Anisotropy", "AppliedTransform", "BiasField", "Blur", "Choice", "Compose", "Contour", "Crop", "ElasticDeformation", "Flip",
-    "Gamma", "GridSampler", "Image", "ImagesBatch", "ImagesLoader", "IntensityTransform", "KeepLargestComponent", "LabelMap", "LabelSampler", "Motion", "Noise", "OneHot", "OneOf",
-    "Pad", "PatchAggregator", "PatchLocation", "PatchSampler", "Queue", "RemapLabels", "RemoveLabels", "Resample", "Resize", "ScalarImage", "SequentialLabels", "SomeOf", "Spatial", "SpatialTransform", "Subject",
-    "SubjectsBatch", "SubjectsLoader", "Transform", "UniformSampler", "WeightedSampler", "apply_inverse_transform", "calibrate_draw_policy", "get_draw_policy", "set_draw_policy", "get_noise_plan", "set_noise_plan", "get_inverse_transform", "get_noise_rng", "get_resample_precision", "get_stencil_precision", "set_noise_rng", "set_resample_precision", "set_stencil_precision",
+    "Affine", "AffineMatrix", "Anisotropy", "AppliedTransform", "BiasField", "Blur", "Choice", "Clamp", "Compose", "Contour", "Crop", "ElasticDeformation", "Flip",
+    "Gamma", "GridSampler", "Image", "ImagesBatch", "ImagesLoader", "IntensityTransform", "KeepLargestComponent", "LabelMap", "LabelSampler", "Mask", "Motion", "Noise", "Normalize", "OneHot", "OneOf",
+    "Pad", "PatchAggregator", "PatchLocation", "PatchSampler", "Queue", "RemapLabels", "RemoveLabels", "Resample", "RescaleIntensity", "Resize", "ScalarImage", "SequentialLabels", "SomeOf", "Spatial", "SpatialTransform", "Standardize", "Subject",
+    "SubjectsBatch", "SubjectsLoader", "Transform", "UniformSampler", "WeightedSampler", "ZNormalization", "apply_inverse_transform", "calibrate_draw_policy", "get_draw_policy", "set_draw_policy", "get_noise_plan", "set_noise_plan", "get_inverse_transform", "get_noise_rng", "get_resample_precision", "get_stencil_precision", "set_noise_rng", "set_resample_precision", "set_stencil_precision",
 ]

@@ -26,6 +26,8 @@ PAD_CONSTANT, PAD_REFLECT, PAD_REPLICATE, PAD_CIRCULAR = 0, 1, 2, 3
 REMAP_KEEP, REMAP_CONSTANT = 0, 1
 REMAP_MAX_PAIRS = 65536
 KEEP_LARGEST_MAX_LABELS = 1024
+# tio_map_mode
+MAP_RESCALE_CLIP, MAP_RESCALE, MAP_SUB_DIV, MAP_MUL_ADD = 0, 1, 2, 3
 # tio_precision
 PRECISION_EXACT, PRECISION_FAST, PRECISION_TIGHT = 0, 1, 2
 GEOM_LARGE_BOXES = 1  # tio_resample_geom.flags (ABI 14): SOME bricks' boxes exceed the staging tile
@@ -187,6 +189,24 @@ HIP_ONLY_PROTOTYPES = {
         [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _I32x3, C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_int64,
          C.c_void_p],
     ),
+    # Normalize / Standardize / Clamp / Mask with on-device statistics (additive to ABI 17): no CPU restatement either
+    "intensity_stats_workspace_bytes": (C.c_int64, []),
+    "intensity_moments": (
+        C.c_int,
+        [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
+    ),
+    "intensity_quantiles": (
+        C.c_int,
+        [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_int32, C.c_void_p,
+         C.c_void_p, C.c_int64, C.c_void_p],
+    ),
+    "intensity_map": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+         C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "intensity_clamp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_void_p]),
+    "intensity_mask": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_void_p]),
 }
 
 #: every symbol include/tio_hip.h declares for libtio_hip.so

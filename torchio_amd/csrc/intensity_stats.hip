@@ -1,0 +1,688 @@
+// intensity_stats.hip — intensity preprocessing (reference transforms/intensity/normalize.py, standardize.py, clamp.py,
+// mask.py) with the statistics computed on the device:
+//   tio_intensity_moments    masked count / mean / unbiased standard deviation: float64 accumulation, per-block partials in
+//                            fixed slots merged in a fixed order (bitwise reproducible, no float atomics);
+//   tio_intensity_quantiles  exact order statistics by a three-pass radix select (11 / 11 / 10 bits) over an order-preserving
+//                            32-bit key of the float32 value, the rank arithmetic on the device;
+//   tio_intensity_map        the four linear maps, every step a separately rounded float32 operation, IEEE division;
+//   tio_intensity_clamp      torch.clamp(min=, max=) with Python-float bounds;
+//   tio_intensity_mask       torch.where(mask, x, python_float), the mask broadcast over batch and channels.
+// Every kernel reads every dtype code and converts to float32 first, as `.float()` does.
+#include "common.hpp"
+
+#include <math.h>
+#include <string.h>
+
+namespace tio {
+namespace {
+
+// ---- the optional mask: nonzero means inside (`.bool()`: -0.0 is outside, NaN inside) ---------------------------------
+struct MaskView {
+  const void* data;   // nullptr: every element is inside
+  int element_size;   // 1, 2, 4, 8
+  int is_float;       // the sign bit does not count
+  int64_t period;     // elements of the mask: the data index modulo this is the mask index
+};
+
+__device__ __forceinline__ bool mask_nonzero(const MaskView& m, int64_t i) {
+  switch (m.element_size) {
+    case 1: return static_cast<const uint8_t*>(m.data)[i] != 0;
+    case 2: {
+      const uint16_t bits = static_cast<const uint16_t*>(m.data)[i];
+      return (m.is_float ? (bits & 0x7FFFu) : bits) != 0;
+    }
+    case 4: {
+      const uint32_t bits = static_cast<const uint32_t*>(m.data)[i];
+      return (m.is_float ? (bits & 0x7FFFFFFFu) : bits) != 0;
+    }
+    default: {
+      const uint64_t bits = static_cast<const uint64_t*>(m.data)[i];
+      return (m.is_float ? (bits & 0x7FFFFFFFFFFFFFFFull) : bits) != 0;
+    }
+  }
+}
+
+// f(float) for every inside element of x[0 : n], 16 bytes of x per load where x allows (the elements in front of the first
+// 16-byte boundary and behind the last whole vector go one by one).  The order in which ONE thread sees its elements is a
+// function of n, the grid and the pointer's offset from a 16-byte boundary alone.
+template <int DT, typename F>
+__device__ __forceinline__ void for_each_inside(const void* x_, int64_t n, const MaskView& mask, F f) {
+  using T = typename Elem<DT>::type;
+  constexpr int PER = 16 / sizeof(T);
+  const T* x = static_cast<const T*>(x_);
+  int64_t head = static_cast<int64_t>(((16 - reinterpret_cast<uintptr_t>(x) % 16) % 16) / sizeof(T));
+  if (head > n) head = n;
+  const int64_t vectors = (n - head) / PER;
+  const int64_t tid = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x, threads = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  const uint4* xv = reinterpret_cast<const uint4*>(x + head);
+  for (int64_t v = tid; v < vectors; v += threads) {
+    const uint4 raw = xv[v];
+    T e[PER];
+    __builtin_memcpy(e, &raw, 16);
+    const int64_t base = head + v * PER;
+    if (mask.data == nullptr) {
+#pragma unroll
+      for (int j = 0; j < PER; j++) f(Elem<DT>::load(e, j));
+    } else {
+      int64_t at = base % mask.period;
+#pragma unroll
+      for (int j = 0; j < PER; j++) {
+        if (mask_nonzero(mask, at)) f(Elem<DT>::load(e, j));
+        if (++at == mask.period) at = 0;
+      }
+    }
+  }
+  const int64_t behind = head + vectors * PER;
+  for (int64_t i = tid; i < head + (n - behind); i += threads) {
+    const int64_t at = i < head ? i : behind + (i - head);
+    if (mask.data == nullptr || mask_nonzero(mask, at % mask.period)) f(Elem<DT>::load(x, at));
+  }
+}
+
+unsigned reduce_blocks(int64_t n, int cap) {
+  const int64_t blocks = (n + 256 * 16 - 1) / (256 * 16);  // 16 elements per thread before a second block pays
+  return static_cast<unsigned>(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
+}
+
+// ---- masked moments --------------------------------------------------------------------------------------------------
+// (count, mean, M2 = sum of squared deviations from the mean) in float64.  A thread sums (x - K) and (x - K)^2 with K its
+// first value — a sample of the distribution, so the squares are of the spread's size and `ss - s^2 / n` cancels nothing
+// that matters —; threads, then blocks, then the block partials are merged pairwise (Chan et al.) in an order that depends
+// on the launch geometry alone.  Infinities and NaN come out as torch has them: a mean of +-inf (NaN when both signs or a NaN
+// are present) and a NaN deviation.
+constexpr int kMomentBlocks = 1024;
+
+struct Moments {
+  double n, mean, m2;
+};
+
+__device__ __forceinline__ Moments merge(const Moments& a, const Moments& b) {
+  if (b.n == 0.0) return a;
+  if (a.n == 0.0) return b;
+  Moments r;
+  r.n = a.n + b.n;
+  const double delta = b.mean - a.mean;
+  if (!(fabs(delta) <= 1.7976931348623157e308)) {  // an infinite or NaN mean on a side: inf + finite = inf, inf - inf = NaN
+    r.mean = a.mean + b.mean;
+    r.m2 = __longlong_as_double(0x7FF8000000000000ll);
+    return r;
+  }
+  r.mean = a.mean + delta * (b.n / r.n);
+  r.m2 = a.m2 + b.m2 + delta * delta * (a.n * (b.n / r.n));
+  return r;
+}
+
+__device__ __forceinline__ Moments block_merge(Moments mine, Moments* lds) {
+  lds[threadIdx.x] = mine;
+  __syncthreads();
+  for (int stride = 128; stride > 0; stride >>= 1) {
+    if (static_cast<int>(threadIdx.x) < stride) lds[threadIdx.x] = merge(lds[threadIdx.x], lds[threadIdx.x + stride]);
+    __syncthreads();
+  }
+  return lds[0];
+}
+
+template <int DT>
+__global__ __launch_bounds__(256) void moments_partial_kernel(const void* __restrict__ x, int64_t n, MaskView mask, Moments* __restrict__ partial) {
+  __shared__ Moments lds[256];
+  double count = 0.0, shift = 0.0, s = 0.0, ss = 0.0;
+  bool shifted = false;
+  for_each_inside<DT>(x, n, mask, [&](float v) {
+    if (!shifted && fabsf(v) <= 3.4028234663852886e38f) {  // the first FINITE value (inf - inf would make a NaN of an infinite mean)
+      shift = static_cast<double>(v);
+      shifted = true;
+      // (what was summed before is infinite or NaN and stays so whatever the shift)
+    }
+    const double d = static_cast<double>(v) - shift;
+    count += 1.0;
+    s += d;
+    ss += d * d;
+  });
+  Moments mine = {0.0, 0.0, 0.0};
+  if (count > 0.0) {
+    mine.n = count;
+    mine.mean = shift + s / count;
+    mine.m2 = ss - s * (s / count);
+  }
+  const Moments all = block_merge(mine, lds);
+  if (threadIdx.x == 0) partial[blockIdx.x] = all;
+}
+
+struct MomentsRecord {
+  int64_t count;
+  float mean, std;
+};
+
+__global__ __launch_bounds__(256) void moments_final_kernel(const Moments* __restrict__ partial, int n_partials, MomentsRecord* __restrict__ record) {
+  __shared__ Moments lds[256];
+  Moments mine = {0.0, 0.0, 0.0};
+  for (int i = threadIdx.x; i < n_partials; i += 256) mine = merge(mine, partial[i]);
+  const Moments all = block_merge(mine, lds);
+  if (threadIdx.x == 0) {
+    record->count = static_cast<int64_t>(all.n);
+    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    // torch: the mean of nothing and the unbiased deviation of one value are NaN.  Only a finite negative m2 (rounding) is
+    // clamped: a NaN m2 — a NaN or an infinity among the values — must stay NaN (fmax would return the other operand)
+    const double mean = all.n > 0.0 ? all.mean : nan;
+    const double m2 = all.m2 < 0.0 ? 0.0 : all.m2;
+    const double variance = all.n > 1.0 ? m2 / (all.n - 1.0) : nan;
+    record->mean = static_cast<float>(mean);          // the one rounding to float32
+    record->std = static_cast<float>(sqrt(variance));
+  }
+}
+
+// ---- exact selection -------------------------------------------------------------------------------------------------
+// key: ascending unsigned order = ascending float order, -0 directly below +0, every NaN at the top (torch.kthvalue sorts
+// NaN last).
+__device__ __forceinline__ uint32_t select_key(float f) {
+  if (f != f) return 0xFFFFFFFFu;
+  const uint32_t bits = __float_as_uint(f);
+  return (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);
+}
+__device__ __forceinline__ float select_value(uint32_t key) {
+  if (key == 0xFFFFFFFFu) return __uint_as_float(0x7FC00000u);
+  return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
+}
+
+constexpr int kSelectBins = 2048, kSelectRanks = 4, kSelectBlocks = 2048;
+
+struct SelectState {
+  unsigned long long n;                    // inside elements (pass 1's total)
+  unsigned long long rank[kSelectRanks];   // 0-based rank of distinct rank r among the elements that share prefix[r]
+  uint32_t prefix[kSelectRanks];           // the key bits resolved so far
+  int32_t n_ranks;                         // distinct ranks, 0 when n == 0
+  int32_t slot[kSelectRanks];              // (q0 lower, q0 upper, q1 lower, q1 upper) -> distinct rank
+};
+
+struct QuantileRecord {
+  float lower, upper;
+  int64_t n;
+};
+
+// Equal digits in a row become one LDS atomic: a constant volume or a block of exact zeros sends every element of a
+// thread to the same bin, and 64 lanes adding to one address go through the LDS one after the other.
+struct RunAdd {
+  int digit = -1;
+  unsigned count = 0;
+  __device__ __forceinline__ void add(unsigned* hist, int d) {
+    if (d == digit) {
+      count++;
+    } else {
+      if (count) atomicAdd(hist + digit, count);
+      digit = d;
+      count = 1;
+    }
+  }
+  __device__ __forceinline__ void flush(unsigned* hist) {
+    if (count) atomicAdd(hist + digit, count);
+    count = 0;
+  }
+};
+
+// PASS 1: the top 11 bits of every inside element (one histogram); PASS 2 / 3: the next 11 / the last 10 bits of the
+// elements whose higher bits are a rank's prefix, one histogram per distinct rank.
+template <int DT, int PASS>
+__global__ __launch_bounds__(256) void select_histogram_kernel(const void* __restrict__ x, int64_t n, MaskView mask,
+                                                               const SelectState* __restrict__ state, unsigned long long* __restrict__ hist) {
+  constexpr int HISTS = PASS == 1 ? 1 : kSelectRanks;
+  constexpr int SHIFT = PASS == 1 ? 21 : (PASS == 2 ? 10 : 0);   // the digit's position
+  constexpr int ABOVE = PASS == 2 ? 21 : 10;                     // bits below the prefix of passes 2 and 3
+  constexpr uint32_t DIGIT_MASK = PASS == 3 ? 0x3FFu : 0x7FFu;
+  __shared__ unsigned lds[HISTS * kSelectBins];
+  const int n_ranks = PASS == 1 ? 1 : state->n_ranks;
+  for (int i = threadIdx.x; i < n_ranks * kSelectBins; i += 256) lds[i] = 0u;
+  uint32_t prefix[kSelectRanks] = {0u, 0u, 0u, 0u};
+  if (PASS != 1) {
+#pragma unroll
+    for (int r = 0; r < kSelectRanks; r++) prefix[r] = r < n_ranks ? state->prefix[r] : 0u;
+  }
+  __syncthreads();
+  if (n_ranks == 0) return;  // (uniform: nothing is inside)
+  RunAdd run[HISTS];
+  for_each_inside<DT>(x, n, mask, [&](float v) {
+    const uint32_t key = select_key(v);
+    if (PASS == 1) {
+      run[0].add(lds, static_cast<int>(key >> SHIFT));
+    } else {
+#pragma unroll
+      for (int r = 0; r < HISTS; r++)
+        if (r < n_ranks && ((key ^ prefix[r]) >> ABOVE) == 0u) run[r].add(lds + r * kSelectBins, static_cast<int>((key >> SHIFT) & DIGIT_MASK));
+    }
+  });
+#pragma unroll
+  for (int r = 0; r < HISTS; r++) run[r].flush(lds + r * kSelectBins);
+  __syncthreads();
+  for (int i = threadIdx.x; i < n_ranks * kSelectBins; i += 256)
+    if (lds[i]) atomicAdd(hist + i, static_cast<unsigned long long>(lds[i]));  // integer sums: the order does not matter
+}
+
+// Inside one block of 256 threads: each owns 8 consecutive bins of a 2048-bin histogram.  scan_bins leaves the thread's bins in
+// `mine` and the sum of all bins in front of them in `*before` (scan[255] is the histogram's total afterwards); find_bin has the
+// thread whose bins hold `rank` (0-based, below the total) write the bin and the rank inside it.
+constexpr int kOwnBins = kSelectBins / 256;
+
+__device__ __forceinline__ void scan_bins(const unsigned long long* hist, unsigned long long* scan, unsigned long long mine[kOwnBins],
+                                          unsigned long long* before) {
+  unsigned long long sum = 0ull;
+#pragma unroll
+  for (int j = 0; j < kOwnBins; j++) {
+    mine[j] = hist[threadIdx.x * kOwnBins + j];
+    sum += mine[j];
+  }
+  __syncthreads();  // (the previous user of `scan` has read it)
+  scan[threadIdx.x] = sum;
+  __syncthreads();
+  for (int offset = 1; offset < 256; offset <<= 1) {
+    const unsigned long long add = static_cast<int>(threadIdx.x) >= offset ? scan[threadIdx.x - offset] : 0ull;
+    __syncthreads();
+    scan[threadIdx.x] += add;
+    __syncthreads();
+  }
+  *before = scan[threadIdx.x] - sum;
+}
+
+__device__ __forceinline__ void find_bin(unsigned long long rank, const unsigned long long mine[kOwnBins], unsigned long long before,
+                                         int* found_bin, unsigned long long* found_rank) {
+#pragma unroll
+  for (int j = 0; j < kOwnBins; j++) {
+    if (rank >= before && rank < before + mine[j]) {
+      *found_bin = static_cast<int>(threadIdx.x) * kOwnBins + j;
+      *found_rank = rank - before;
+    }
+    before += mine[j];
+  }
+  __syncthreads();
+}
+
+// One block after each data pass: narrows every rank's prefix, zeroes the histograms the pass has used for the next pass, and
+// — after pass 3 — writes the records.  Pass 1 also turns the fractions into ranks: lower = floor(q * (n - 1)) with the two
+// float64 operations of the reference's compute_quantile, upper = min(lower + 1, n - 1).
+template <int PASS>
+__global__ __launch_bounds__(256) void select_scan_kernel(SelectState* state, unsigned long long* hist, double q0, double q1, int n_q,
+                                                          QuantileRecord* __restrict__ record) {
+  __shared__ unsigned long long scan[256];
+  __shared__ int found_bin;
+  __shared__ unsigned long long found_rank;
+  __shared__ unsigned long long want[kSelectRanks];
+  __shared__ int n_want;
+  unsigned long long mine[kOwnBins], before;
+  int n_ranks;
+  if (PASS == 1) {
+    scan_bins(hist, scan, mine, &before);  // the one histogram of pass 1 serves every rank
+    if (threadIdx.x == 0) {
+      const unsigned long long n = scan[255];
+      state->n = n;
+      int distinct = 0;
+      if (n > 0ull) {
+        for (int k = 0; k < 2 * n_q; k++) {
+          const double q = k < 2 ? q0 : q1;
+          const double index = q * static_cast<double>(n - 1ull);
+          unsigned long long rank = static_cast<unsigned long long>(floor(index));
+          if (k & 1) rank = rank + 1ull < n ? rank + 1ull : n - 1ull;
+          int at = 0;
+          while (at < distinct && want[at] != rank) at++;
+          if (at == distinct) want[distinct++] = rank;
+          state->slot[k] = at;
+        }
+      }
+      n_want = distinct;
+      state->n_ranks = distinct;
+    }
+    __syncthreads();
+    n_ranks = n_want;
+  } else {
+    n_ranks = state->n_ranks;
+  }
+  for (int r = 0; r < n_ranks; r++) {
+    if (PASS != 1) scan_bins(hist + r * kSelectBins, scan, mine, &before);
+    find_bin(PASS == 1 ? want[r] : state->rank[r], mine, before, &found_bin, &found_rank);
+    if (threadIdx.x == 0) {
+      const uint32_t digit = static_cast<uint32_t>(found_bin);
+      state->prefix[r] = PASS == 1 ? digit << 21 : (PASS == 2 ? state->prefix[r] | (digit << 10) : state->prefix[r] | digit);
+      state->rank[r] = found_rank;
+    }
+    __syncthreads();
+  }
+  // what this pass's data kernel has added to: pass 1 one histogram, pass 2 one per rank; after pass 3 nothing reads them again
+  if (PASS != 3)
+    for (int i = threadIdx.x; i < (PASS == 1 ? 1 : n_ranks) * kSelectBins; i += 256) hist[i] = 0ull;
+  if (PASS == 3 && static_cast<int>(threadIdx.x) < n_q) {
+    QuantileRecord out;
+    out.n = static_cast<int64_t>(state->n);
+    if (n_ranks == 0) {
+      out.lower = out.upper = __uint_as_float(0x7FC00000u);
+    } else {
+      out.lower = select_value(state->prefix[state->slot[2 * threadIdx.x]]);
+      out.upper = select_value(state->prefix[state->slot[2 * threadIdx.x + 1]]);
+    }
+    record[threadIdx.x] = out;
+  }
+}
+
+constexpr int64_t kSelectHistBytes = static_cast<int64_t>(kSelectRanks) * kSelectBins * sizeof(unsigned long long);
+constexpr int64_t kStatsWorkspaceBytes = kSelectHistBytes + 256;  // the histograms, then the state
+static_assert(kStatsWorkspaceBytes >= static_cast<int64_t>(kMomentBlocks * sizeof(Moments)), "the moments' partials share the workspace");
+static_assert(sizeof(SelectState) <= 256, "the state's place in the workspace");
+
+// ---- elementwise streams: y[i] = f(x[i], i), TI in, TO out, 16 bytes per access on the narrower side where both pointers
+// allow it (a group of G elements: 16 bytes of the narrower type); otherwise element by element ------------------------
+template <typename TI, typename TO, typename F>
+__device__ __forceinline__ void stream_convert(const TI* x, TO* y, int64_t n, F f) {
+  constexpr int NARROW = sizeof(TI) < sizeof(TO) ? sizeof(TI) : sizeof(TO);
+  constexpr int G = 16 / NARROW;
+  constexpr int AI = G * sizeof(TI) < 16 ? G * sizeof(TI) : 16, AO = G * sizeof(TO) < 16 ? G * sizeof(TO) : 16;
+  const uintptr_t ax = reinterpret_cast<uintptr_t>(x), ay = reinterpret_cast<uintptr_t>(y);
+  int64_t head = n;  // no common boundary: everything goes one by one
+  for (int h = 0; h < G; h++) {
+    if ((ax + h * sizeof(TI)) % AI == 0 && (ay + h * sizeof(TO)) % AO == 0) {
+      head = h < n ? h : n;
+      break;
+    }
+  }
+  const int64_t groups = (n - head) / G;
+  const int64_t tid = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x, threads = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  for (int64_t g = tid; g < groups; g += threads) {
+    const int64_t base = head + g * G;
+    TI in[G];
+    TO out[G];
+    __builtin_memcpy(in, __builtin_assume_aligned(x + base, AI), G * sizeof(TI));
+#pragma unroll
+    for (int j = 0; j < G; j++) out[j] = f(in[j], base + j);
+    __builtin_memcpy(__builtin_assume_aligned(y + base, AO), out, G * sizeof(TO));
+  }
+  const int64_t behind = head + groups * G;
+  for (int64_t i = tid; i < head + (n - behind); i += threads) {
+    const int64_t at = i < head ? i : behind + (i - head);
+    y[at] = f(x[at], at);
+  }
+}
+
+unsigned stream_blocks(int64_t n) {
+  const int64_t blocks = (n / 4 + 255) / 256;
+  return static_cast<unsigned>(blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks));
+}
+
+// ---- the linear maps -------------------------------------------------------------------------------------------------
+struct MapParams {
+  int mode;
+  float in_min, in_max, in_range, out_min, out_range;
+  const float* out_min_dev;    // (B,) or nullptr: the scalars
+  const float* out_range_dev;
+  int64_t n_per_element;
+};
+
+// torch.clamp: a NaN stays a NaN, the bounds are applied as min(max(x, lo), hi)
+__device__ __forceinline__ float clip(float v, float lo, float hi) { return v != v ? v : fminf(fmaxf(v, lo), hi); }
+
+template <int DT>
+__global__ __launch_bounds__(256) void map_kernel(const typename Elem<DT>::type* __restrict__ x, float* __restrict__ y, int64_t n, MapParams p) {
+  using T = typename Elem<DT>::type;
+  int64_t lo = 0, hi = 0;  // the batch element of the last index seen: its range of indices and its parameters
+  float out_min = p.out_min, out_range = p.out_range;
+  stream_convert<T, float>(x, y, n, [&](T raw, int64_t i) {
+    const float v = Elem<DT>::load(&raw, 0);
+    if (p.out_min_dev != nullptr && (i < lo || i >= hi)) {
+      const int64_t b = i / p.n_per_element;
+      lo = b * p.n_per_element;
+      hi = lo + p.n_per_element;
+      out_min = p.out_min_dev[b];
+      out_range = p.out_range_dev[b];
+    }
+    // (-ffp-contract=off: each operation below rounds to float32 on its own, the division is IEEE)
+    switch (p.mode) {
+      case TIO_MAP_RESCALE_CLIP: return (clip(v, p.in_min, p.in_max) - p.in_min) / p.in_range * out_range + out_min;
+      case TIO_MAP_RESCALE:
+        if (p.out_min_dev != nullptr && out_range == 0.0f) return v;  // _RescaleInverse: such an element stays
+        return (v - out_min) / out_range * p.in_range + p.in_min;
+      case TIO_MAP_SUB_DIV: return (v - p.in_min) / p.in_range;
+      default: return v * p.in_range + p.in_min;
+    }
+  });
+}
+
+// ---- clamp and mask: the result dtype of torch's type promotion with a Python float ------------------------------------
+//   float64 stays float64 (compared in float64), float16 / bfloat16 / float32 stay (the scalar is cast to the dtype; the
+//   comparison of two such values in float32 is the comparison in the dtype), every integer dtype becomes float32.
+template <int DT>
+struct Promoted {
+  using Out = float;
+  using Work = float;
+  static __device__ __forceinline__ Work load(typename Elem<DT>::type v) { return Elem<DT>::load(&v, 0); }
+  static __device__ __forceinline__ Out store(Work v) { return v; }
+};
+template <>
+struct Promoted<TIO_F64> {
+  using Out = double;
+  using Work = double;
+  static __device__ __forceinline__ Work load(double v) { return v; }
+  static __device__ __forceinline__ Out store(Work v) { return v; }
+};
+template <>
+struct Promoted<TIO_F16> {
+  using Out = _Float16;
+  using Work = float;
+  static __device__ __forceinline__ Work load(_Float16 v) { return static_cast<float>(v); }
+  static __device__ __forceinline__ Out store(Work v) { return static_cast<_Float16>(v); }  // (v is a float16 value: exact)
+};
+template <>
+struct Promoted<TIO_BF16> {
+  using Out = uint16_t;
+  using Work = float;
+  static __device__ __forceinline__ Work load(uint16_t v) { return bf16_bits_to_float(v); }
+  static __device__ __forceinline__ Out store(Work v) { return float_to_bf16_bits(v); }  // (exact likewise)
+};
+
+template <int DT>
+__global__ __launch_bounds__(256) void clamp_kernel(const typename Elem<DT>::type* __restrict__ x, typename Promoted<DT>::Out* __restrict__ y, int64_t n,
+                                                    int has_min, double lo_, int has_max, double hi_) {
+  using P = Promoted<DT>;
+  using W = typename P::Work;
+  const W lo = static_cast<W>(lo_), hi = static_cast<W>(hi_);
+  stream_convert<typename Elem<DT>::type, typename P::Out>(x, y, n, [&](typename Elem<DT>::type raw, int64_t) {
+    W v = P::load(raw);
+    if (v == v) {
+      if (has_min) v = v < lo ? lo : v;
+      if (has_max) v = v > hi ? hi : v;
+    }
+    return P::store(v);
+  });
+}
+
+template <int DT>
+__global__ __launch_bounds__(256) void mask_kernel(const typename Elem<DT>::type* __restrict__ x, typename Promoted<DT>::Out* __restrict__ y, int64_t n,
+                                                   MaskView mask, double outside_) {
+  using P = Promoted<DT>;
+  const typename P::Out outside = P::store(static_cast<typename P::Work>(outside_));
+  int64_t last = -2, at = 0;  // consecutive indices walk the mask without a division
+  stream_convert<typename Elem<DT>::type, typename P::Out>(x, y, n, [&](typename Elem<DT>::type raw, int64_t i) {
+    if (i != last + 1) at = i % mask.period;
+    else if (++at == mask.period) at = 0;
+    last = i;
+    return mask_nonzero(mask, at) ? P::store(P::load(raw)) : outside;
+  });
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------
+bool known_dtype(int dtype) { return dtype >= 0 && dtype <= TIO_I64 && dtype_size(dtype) != 0; }
+
+// a Python float as the dtype's scalar (c10::Scalar::to<T>: through float32 for the 16-bit floats), back as a double
+double scalar_in_dtype(double v, int dtype) {
+  if (dtype == TIO_F64) return v;
+  float f = static_cast<float>(v);
+  if (dtype == TIO_F16) f = static_cast<float>(static_cast<_Float16>(f));
+  if (dtype == TIO_BF16 && f == f) {
+    uint32_t bits;
+    memcpy(&bits, &f, 4);
+    bits += 0x7FFFu + ((bits >> 16) & 1u);
+    bits &= 0xFFFF0000u;
+    memcpy(&f, &bits, 4);
+  }
+  return static_cast<double>(f);
+}
+
+// the checks the two statistics share; *n is channels * n_spatial
+int check_stats_arguments(const char* who, const void* x, int dtype, int channels, int64_t n_spatial, const void* mask, int mask_dtype,
+                          int mask_channels, const void* record, const void* workspace, int64_t workspace_bytes, MaskView* view, int64_t* n) {
+  if (!known_dtype(dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "%s: unknown dtype %d", who, dtype);
+  if (mask != nullptr && !known_dtype(mask_dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "%s: unknown mask dtype %d", who, mask_dtype);
+  if (channels < 0 || n_spatial < 0) return fail(TIO_ERR_INVALID_ARGUMENT, "%s: negative size", who);
+  if (mask != nullptr && mask_channels != 1 && mask_channels != channels)
+    return fail(TIO_ERR_INVALID_ARGUMENT, "%s: %d mask channels for %d data channels (1 or as many)", who, mask_channels, channels);
+  if (record == nullptr || workspace == nullptr) return fail(TIO_ERR_INVALID_ARGUMENT, "%s: null record or workspace", who);
+  if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0 || reinterpret_cast<uintptr_t>(record) % 8 != 0)
+    return fail(TIO_ERR_INVALID_ARGUMENT, "%s: the workspace must be 16-byte aligned, the record 8-byte", who);
+  if (workspace_bytes < kStatsWorkspaceBytes)
+    return fail(TIO_ERR_INVALID_ARGUMENT, "%s: workspace of %lld bytes is too small", who, static_cast<long long>(workspace_bytes));
+  if (channels > 0 && n_spatial > (int64_t{1} << 40) / channels) return fail(TIO_ERR_UNSUPPORTED_CONFIG, "%s: more than 2^40 elements", who);
+  *n = static_cast<int64_t>(channels) * n_spatial;
+  if (*n > 0 && x == nullptr) return fail(TIO_ERR_INVALID_ARGUMENT, "%s: null data", who);
+  view->data = *n > 0 ? mask : nullptr;
+  view->element_size = mask != nullptr ? dtype_size(mask_dtype) : 1;
+  view->is_float = mask != nullptr && is_float_dtype(mask_dtype);
+  view->period = mask != nullptr && mask_channels * n_spatial > 0 ? mask_channels * n_spatial : 1;
+  return TIO_OK;
+}
+
+}  // namespace
+}  // namespace tio
+
+#define TIO_FOR_EACH_DTYPE(dtype, CASE) \
+  switch (dtype) {                      \
+    case TIO_F32: CASE(TIO_F32); break; \
+    case TIO_F64: CASE(TIO_F64); break; \
+    case TIO_F16: CASE(TIO_F16); break; \
+    case TIO_BF16: CASE(TIO_BF16); break; \
+    case TIO_U8: CASE(TIO_U8); break;   \
+    case TIO_I8: CASE(TIO_I8); break;   \
+    case TIO_I16: CASE(TIO_I16); break; \
+    case TIO_I32: CASE(TIO_I32); break; \
+    default: CASE(TIO_I64); break;      \
+  }
+
+extern "C" int64_t tio_intensity_stats_workspace_bytes(void) { return tio::kStatsWorkspaceBytes; }
+
+extern "C" int tio_intensity_moments(const void* x, int32_t dtype, int32_t channels, int64_t n_spatial, const void* mask, int32_t mask_dtype,
+                                     int32_t mask_channels, void* record_dev, void* workspace_dev, int64_t workspace_bytes, void* stream) {
+  using namespace tio;
+  MaskView view;
+  int64_t n = 0;
+  if (const int rc = check_stats_arguments("tio_intensity_moments", x, dtype, channels, n_spatial, mask, mask_dtype, mask_channels, record_dev,
+                                           workspace_dev, workspace_bytes, &view, &n))
+    return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  Moments* partial = static_cast<Moments*>(workspace_dev);
+  const unsigned blocks = reduce_blocks(n, kMomentBlocks);
+#define TIO_MOMENTS(DT) hipLaunchKernelGGL(moments_partial_kernel<DT>, dim3(blocks), dim3(256), 0, s, x, n, view, partial)
+  TIO_FOR_EACH_DTYPE(dtype, TIO_MOMENTS)
+#undef TIO_MOMENTS
+  if (const int rc = check_launch("tio_intensity_moments (partials)")) return rc;
+  hipLaunchKernelGGL(moments_final_kernel, dim3(1), dim3(256), 0, s, partial, static_cast<int>(blocks), static_cast<MomentsRecord*>(record_dev));
+  return check_launch("tio_intensity_moments");
+}
+
+extern "C" int tio_intensity_quantiles(const void* x, int32_t dtype, int32_t channels, int64_t n_spatial, const void* mask, int32_t mask_dtype,
+                                       int32_t mask_channels, const double* fractions, int32_t n_fractions, void* record_dev,
+                                       void* workspace_dev, int64_t workspace_bytes, void* stream) {
+  using namespace tio;
+  if (fractions == nullptr || n_fractions < 1 || n_fractions > 2)
+    return fail(TIO_ERR_INVALID_ARGUMENT, "tio_intensity_quantiles: one or two fractions, got %d", n_fractions);
+  for (int k = 0; k < n_fractions; k++)
+    if (!(fractions[k] >= 0.0 && fractions[k] <= 1.0))
+      return fail(TIO_ERR_INVALID_ARGUMENT, "tio_intensity_quantiles: fraction %g outside [0, 1]", fractions[k]);
+  MaskView view;
+  int64_t n = 0;
+  if (const int rc = check_stats_arguments("tio_intensity_quantiles", x, dtype, channels, n_spatial, mask, mask_dtype, mask_channels, record_dev,
+                                           workspace_dev, workspace_bytes, &view, &n))
+    return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  unsigned long long* hist = static_cast<unsigned long long*>(workspace_dev);
+  SelectState* state = reinterpret_cast<SelectState*>(static_cast<char*>(workspace_dev) + kSelectHistBytes);
+  QuantileRecord* record = static_cast<QuantileRecord*>(record_dev);
+  // (the workspace may hold anything: zeroed once here; between the passes the scan kernels zero what the pass has used)
+  if (hipMemsetAsync(hist, 0, kSelectHistBytes, s) != hipSuccess) return fail(TIO_ERR_LAUNCH, "tio_intensity_quantiles: memset failed");
+  const dim3 grid(reduce_blocks(n, kSelectBlocks)), block(256);
+  const double q0 = fractions[0], q1 = n_fractions > 1 ? fractions[1] : fractions[0];
+#define TIO_SELECT_1(DT) hipLaunchKernelGGL((select_histogram_kernel<DT, 1>), grid, block, 0, s, x, n, view, state, hist)
+#define TIO_SELECT_2(DT) hipLaunchKernelGGL((select_histogram_kernel<DT, 2>), grid, block, 0, s, x, n, view, state, hist)
+#define TIO_SELECT_3(DT) hipLaunchKernelGGL((select_histogram_kernel<DT, 3>), grid, block, 0, s, x, n, view, state, hist)
+  TIO_FOR_EACH_DTYPE(dtype, TIO_SELECT_1)
+  if (const int rc = check_launch("tio_intensity_quantiles (pass 1)")) return rc;
+  hipLaunchKernelGGL(select_scan_kernel<1>, dim3(1), block, 0, s, state, hist, q0, q1, n_fractions, record);
+  if (const int rc = check_launch("tio_intensity_quantiles (scan 1)")) return rc;
+  TIO_FOR_EACH_DTYPE(dtype, TIO_SELECT_2)
+  if (const int rc = check_launch("tio_intensity_quantiles (pass 2)")) return rc;
+  hipLaunchKernelGGL(select_scan_kernel<2>, dim3(1), block, 0, s, state, hist, q0, q1, n_fractions, record);
+  if (const int rc = check_launch("tio_intensity_quantiles (scan 2)")) return rc;
+  TIO_FOR_EACH_DTYPE(dtype, TIO_SELECT_3)
+  if (const int rc = check_launch("tio_intensity_quantiles (pass 3)")) return rc;
+  hipLaunchKernelGGL(select_scan_kernel<3>, dim3(1), block, 0, s, state, hist, q0, q1, n_fractions, record);
+#undef TIO_SELECT_1
+#undef TIO_SELECT_2
+#undef TIO_SELECT_3
+  return check_launch("tio_intensity_quantiles");
+}
+
+extern "C" int tio_intensity_map(const void* x, float* y, int32_t dtype, int32_t batch, int64_t n_per_element, int32_t mode, float in_min,
+                                 float in_max, float in_range, float out_min, float out_range, const float* out_min_dev,
+                                 const float* out_range_dev, void* stream) {
+  using namespace tio;
+  if (!known_dtype(dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_intensity_map: unknown dtype %d", dtype);
+  if (batch < 0 || n_per_element < 0) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_intensity_map: negative size");
+  if (mode < TIO_MAP_RESCALE_CLIP || mode > TIO_MAP_MUL_ADD) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_intensity_map: unknown mode %d", mode);
+  if ((out_min_dev == nullptr) != (out_range_dev == nullptr))
+    return fail(TIO_ERR_INVALID_ARGUMENT, "tio_intensity_map: per-element out_min and out_range come together");
+  if (out_min_dev != nullptr && mode != TIO_MAP_RESCALE_CLIP && mode != TIO_MAP_RESCALE)
+    return fail(TIO_ERR_INVALID_ARGUMENT, "tio_intensity_map: mode %d takes no per-element parameters", mode);
+  if (batch > 0 && n_per_element > (int64_t{1} << 40) / batch) return fail(TIO_ERR_UNSUPPORTED_CONFIG, "tio_intensity_map: more than 2^40 elements");
+  const int64_t n = static_cast<int64_t>(batch) * n_per_element;
+  if (n == 0) return TIO_OK;
+  if (x == nullptr || y == nullptr) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_intensity_map: null argument");
+  const MapParams p = {mode, in_min, in_max, in_range, out_min, out_range, out_min_dev, out_range_dev, n_per_element};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid(stream_blocks(n)), block(256);
+#define TIO_MAP(DT) hipLaunchKernelGGL(map_kernel<DT>, grid, block, 0, s, static_cast<const Elem<DT>::type*>(x), y, n, p)
+  TIO_FOR_EACH_DTYPE(dtype, TIO_MAP)
+#undef TIO_MAP
+  return check_launch("tio_intensity_map");
+}
+
+extern "C" int tio_intensity_clamp(const void* x, void* y, int32_t dtype, int64_t n, int32_t has_min, double out_min, int32_t has_max,
+                                   double out_max, void* stream) {
+  using namespace tio;
+  if (!known_dtype(dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_intensity_clamp: unknown dtype %d", dtype);
+  if (n < 0) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_intensity_clamp: negative size");
+  if (!has_min && !has_max) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_intensity_clamp: at least one of the bounds");
+  if ((has_min && out_min != out_min) || (has_max && out_max != out_max)) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_intensity_clamp: a bound is NaN");
+  if (n == 0) return TIO_OK;
+  if (x == nullptr || y == nullptr) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_intensity_clamp: null argument");
+  const double lo = scalar_in_dtype(out_min, dtype), hi = scalar_in_dtype(out_max, dtype);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid(stream_blocks(n)), block(256);
+#define TIO_CLAMP(DT) \
+  hipLaunchKernelGGL(clamp_kernel<DT>, grid, block, 0, s, static_cast<const Elem<DT>::type*>(x), static_cast<Promoted<DT>::Out*>(y), n, has_min, lo, has_max, hi)
+  TIO_FOR_EACH_DTYPE(dtype, TIO_CLAMP)
+#undef TIO_CLAMP
+  return check_launch("tio_intensity_clamp");
+}
+
+extern "C" int tio_intensity_mask(const void* x, void* y, int32_t dtype, int64_t n, const void* mask, int32_t mask_dtype, int64_t mask_n,
+                                  double outside_value, void* stream) {
+  using namespace tio;
+  if (!known_dtype(dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_intensity_mask: unknown dtype %d", dtype);
+  if (!known_dtype(mask_dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_intensity_mask: unknown mask dtype %d", mask_dtype);
+  if (n < 0 || mask_n < 0) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_intensity_mask: negative size");
+  if (n == 0) return TIO_OK;
+  if (mask_n == 0 || n % mask_n != 0)
+    return fail(TIO_ERR_INVALID_ARGUMENT, "tio_intensity_mask: %lld data elements are no multiple of %lld mask elements", static_cast<long long>(n),
+                static_cast<long long>(mask_n));
+  if (x == nullptr || y == nullptr || mask == nullptr) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_intensity_mask: null argument");
+  const MaskView view = {mask, dtype_size(mask_dtype), is_float_dtype(mask_dtype) ? 1 : 0, mask_n};
+  const double outside = scalar_in_dtype(outside_value, dtype_size(dtype) != 0 && is_float_dtype(dtype) ? dtype : TIO_F32);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid(stream_blocks(n)), block(256);
+#define TIO_MASK(DT) \
+  hipLaunchKernelGGL(mask_kernel<DT>, grid, block, 0, s, static_cast<const Elem<DT>::type*>(x), static_cast<Promoted<DT>::Out*>(y), n, view, outside)
+  TIO_FOR_EACH_DTYPE(dtype, TIO_MASK)
+#undef TIO_MASK
+  return check_launch("tio_intensity_mask");
+}

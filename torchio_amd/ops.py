@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import collections
 import ctypes as C
+import math
 import os
 import time
 import threading
@@ -1625,6 +1626,163 @@ class Engine:
             # (every chunk works on the original data: a removed voxel never counts for a later chunk's label)
             result = out if result is None else torch.where(out != data, out, result)
         return result
+
+    # -- intensity preprocessing with on-device statistics (normalize.py, standardize.py, clamp.py, mask.py) -------------
+    _MAP_MODES = {"rescale_clip": _abi.MAP_RESCALE_CLIP, "rescale": _abi.MAP_RESCALE, "sub_div": _abi.MAP_SUB_DIV, "mul_add": _abi.MAP_MUL_ADD}
+
+    @staticmethod
+    def _first_element_and_mask(data: Tensor, mask: Tensor | None, what: str) -> tuple[Tensor, Tensor | None]:
+        """``data[0]`` as a dense ``(C, I, J, K)`` tensor and the mask as a dense ``(1 or C, I, J, K)`` one (bool as uint8)."""
+        if data.ndim not in (4, 5):
+            raise ValueError(f"{what}: expected a (B, C, I, J, K) or (C, I, J, K) tensor, got {tuple(data.shape)}")
+        first = (data[0] if data.ndim == 5 else data).contiguous()
+        if mask is not None:
+            if mask.ndim != 4 or tuple(mask.shape[1:]) != tuple(first.shape[1:]) or mask.shape[0] not in (1, first.shape[0]):
+                raise ValueError(f"{what}: a mask of shape {tuple(mask.shape)} does not broadcast over data of shape {tuple(first.shape)}")
+            mask = mask.contiguous()
+            if mask.dtype == torch.bool:
+                mask = mask.view(torch.uint8)
+        return first, mask
+
+    def _statistics_call(self, name: str, first: Tensor, mask: Tensor | None, record_words: int, *extra) -> Tensor:
+        """One statistics launch and its one read-back: the record as int64 words on the host."""
+        record = torch.empty(record_words, dtype=torch.int64, device=first.device)
+        nbytes = int(self._fn["intensity_stats_workspace_bytes"]())
+        workspace = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=first.device)
+        spatial = first.shape[1] * first.shape[2] * first.shape[3]
+        self._call(name, first, _ptr(first), dtype_code(first.dtype), first.shape[0], spatial, _ptr(mask),
+                   0 if mask is None else dtype_code(mask.dtype), 0 if mask is None else mask.shape[0], *extra, _ptr(record), _ptr(workspace),
+                   nbytes, self._stream(first))
+        return record.cpu()
+
+    def intensity_moments(self, data: Tensor, mask: Tensor | None = None) -> tuple[int, float, float]:
+        """``(count, mean, std)`` of ``data[0]`` (all channels) inside ``mask`` — ``values.float().mean()`` / ``.std()`` of the
+        reference's Standardize, accumulated in float64 and rounded once to float32; bitwise reproducible.
+
+        ``mask``: ``(1 or C, I, J, K)`` on the device, any dtype, nonzero = inside.  One read-back of 16 bytes.  ``count == 0``:
+        both NaN; ``count == 1``: ``std`` is NaN, as ``torch.std`` has it.
+        """
+        first, mask = self._first_element_and_mask(data, mask, "intensity_moments")
+        self._check("intensity_moments", first, mask)
+        record = self._statistics_call("intensity_moments", first, mask, 2)
+        mean, std = record[1:].view(torch.float32).tolist()
+        return int(record[0]), mean, std
+
+    def _order_statistics(self, data: Tensor, fractions: Sequence[float], mask: Tensor | None = None) -> list[tuple[Tensor, Tensor, int]]:
+        """Per fraction ``q``: ``(lower_value, upper_value, n)`` — with ``n`` the number of elements of ``data[0]`` inside
+        ``mask`` and ``lower = floor(q * (n - 1))``, the ``(lower + 1)``-th and ``(lower + 2)``-th smallest of them
+        (``torch.kthvalue``'s; the same value twice when ``lower == n - 1``) as 0-dim float32 CPU tensors; NaN when ``n == 0``.
+
+        Selected on the device, two fractions per launch sequence and read-back (32 bytes).
+        """
+        fractions = [float(q) for q in fractions]
+        for q in fractions:
+            if not 0 <= q <= 1:
+                raise ValueError(f"Only values 0 <= q <= 1 are supported, but got {q!r}")
+        first, mask = self._first_element_and_mask(data, mask, "intensity_quantiles")
+        self._check("intensity_quantiles", first, mask)
+        found = []
+        for begin in range(0, len(fractions), 2):
+            chunk = fractions[begin : begin + 2]
+            record = self._statistics_call("intensity_quantiles", first, mask, 2 * len(chunk), (C.c_double * len(chunk))(*chunk), len(chunk))
+            selected = record.view(torch.float32)
+            found += [(selected[4 * k], selected[4 * k + 1], int(record[2 * k + 1])) for k in range(len(chunk))]
+        return found
+
+    def intensity_quantiles(self, data: Tensor, fractions: Sequence[float], mask: Tensor | None = None, *, return_count: bool = False):
+        """``[compute_quantile(values.float(), q) for q in fractions]`` of the reference (``_statistics.py:36-43``) as Python
+        floats, ``values`` being ``data[0]`` inside ``mask``: the order statistics come from the device
+        (``_order_statistics``), the interpolation is the reference's own ``lerp`` on 0-dim CPU tensors.
+
+        Nothing inside the mask: ``ValueError``, or — with ``return_count=True``, which returns ``(values, count)`` — NaNs.
+        """
+        fractions = [float(q) for q in fractions]
+        found = self._order_statistics(data, fractions, mask)
+        count = found[0][2] if found else 0  # (the same for every fraction: the number of inside elements)
+        values: list[float] = []
+        for q, (lower_value, upper_value, _) in zip(fractions, found, strict=True):
+            if count == 0:
+                values.append(math.nan)
+                continue
+            index = q * (count - 1)
+            lower = math.floor(index)
+            value = lower_value if index == lower else lower_value.lerp(upper_value, index - lower)
+            values.append(float(value.item()))
+        if return_count:
+            return values, count
+        if fractions and count == 0:
+            raise ValueError("intensity_quantiles: no element inside the mask")
+        return values
+
+    def intensity_map(self, data: Tensor, mode: str, *, in_min: float = 0.0, in_max: float = 0.0, in_range: float = 1.0,
+                      out_min: float | Tensor = 0.0, out_range: float | Tensor = 1.0) -> Tensor:
+        """One float32 pass over ``data`` of any dtype, every operation rounded on its own like ATen's CPU kernels:
+
+        ``"rescale_clip"``  ``(clamp(x, in_min, in_max) - in_min) / in_range * out_range + out_min``  (Normalize);
+        ``"rescale"``       ``(x - out_min) / out_range * in_range + in_min``  (its inverse);
+        ``"sub_div"``       ``(x - in_min) / in_range``  (Standardize);
+        ``"mul_add"``       ``x * in_range + in_min``  (its inverse).
+
+        ``out_min`` / ``out_range``: numbers, or float32 device tensors with one value per batch element (the rescale modes);
+        with tensors, ``"rescale"`` leaves an element whose ``out_range`` is 0 unchanged.
+        """
+        if mode not in self._MAP_MODES:
+            raise ValueError(f"intensity_map: unknown mode {mode!r} (one of {sorted(self._MAP_MODES)})")
+        if data.ndim < 1:
+            raise ValueError("intensity_map: expected a tensor with a batch dimension")
+        per_element = isinstance(out_min, Tensor)
+        if per_element != isinstance(out_range, Tensor):
+            raise ValueError("intensity_map: out_min and out_range are both numbers or both tensors")
+        data = data.contiguous()
+        batch = data.shape[0]
+        if per_element:
+            if mode not in ("rescale_clip", "rescale"):
+                raise ValueError(f"intensity_map: mode {mode!r} takes no per-element parameters")
+            if out_min.numel() != batch or out_range.numel() != batch or out_min.dtype != torch.float32 or out_range.dtype != torch.float32:
+                raise ValueError(f"intensity_map: per-element out_min / out_range must hold {batch} float32 values")
+            out_min, out_range = out_min.contiguous(), out_range.contiguous()
+            self._check("intensity_map", data, out_min, out_range)
+        else:
+            self._check("intensity_map", data)
+        out = torch.empty(data.shape, dtype=torch.float32, device=data.device)
+        self._call("intensity_map", data, _ptr(data), _ptr(out), dtype_code(data.dtype), batch, data.numel() // batch if batch else 0,
+                   self._MAP_MODES[mode], float(in_min), float(in_max), float(in_range), 0.0 if per_element else float(out_min),
+                   1.0 if per_element else float(out_range), _ptr(out_min) if per_element else None, _ptr(out_range) if per_element else None,
+                   self._stream(data))
+        return out
+
+    @staticmethod
+    def _promoted(dtype: torch.dtype) -> torch.dtype:
+        """torch's result dtype for an op of a tensor with a Python float: floating dtypes stay, integers become float32."""
+        return dtype if dtype in FLOAT_DTYPES else torch.float32
+
+    def clamp(self, data: Tensor, out_min: float | None = None, out_max: float | None = None) -> Tensor:
+        """``data.clamp(min=out_min, max=out_max)`` with Python numbers: NaN propagates, integer data becomes float32."""
+        if out_min is None and out_max is None:
+            raise RuntimeError("torch.clamp: At least one of 'min' or 'max' must not be None")
+        data = data.contiguous()
+        self._check("clamp", data)
+        out = torch.empty(data.shape, dtype=self._promoted(data.dtype), device=data.device)
+        self._call("intensity_clamp", data, _ptr(data), _ptr(out), dtype_code(data.dtype), data.numel(), int(out_min is not None),
+                   0.0 if out_min is None else float(out_min), int(out_max is not None), 0.0 if out_max is None else float(out_max),
+                   self._stream(data))
+        return out
+
+    def mask_where(self, data: Tensor, mask: Tensor, outside_value: float) -> Tensor:
+        """``torch.where(mask.expand_as(data), data, outside_value)``: ``data`` is ``(B, C, I, J, K)``, ``mask`` ``(1 or C, I, J, K)``
+        on the device, any dtype, nonzero = inside; broadcast over the batch (and the channels).  Integer data becomes float32."""
+        if data.ndim != 5:
+            raise ValueError(f"mask_where: expected a (B, C, I, J, K) tensor, got {tuple(data.shape)}")
+        if mask.ndim != 4 or tuple(mask.shape[1:]) != tuple(data.shape[2:]) or mask.shape[0] not in (1, data.shape[1]):
+            raise ValueError(f"mask_where: a mask of shape {tuple(mask.shape)} does not broadcast over data of shape {tuple(data.shape)}")
+        data, mask = data.contiguous(), mask.contiguous()
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+        self._check("mask_where", data, mask)
+        out = torch.empty(data.shape, dtype=self._promoted(data.dtype), device=data.device)
+        self._call("intensity_mask", data, _ptr(data), _ptr(out), dtype_code(data.dtype), data.numel(), _ptr(mask), dtype_code(mask.dtype),
+                   mask.numel(), float(outside_value), self._stream(data))
+        return out
 
     def kspace_segment_mix(self, segments: Sequence[Tensor], bounds: Sequence[int], out_dtype: torch.dtype,
                            active: Tensor | None = None) -> Tensor:

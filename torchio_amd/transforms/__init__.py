@@ -18,6 +18,12 @@ from .motion import Motion
 from .noise import Noise
 from .noise import get_noise_rng
 from .noise import set_noise_rng
+from .normalize import Clamp
+from .normalize import Mask
+from .normalize import Normalize
+from .normalize import RescaleIntensity
+from .normalize import Standardize
+from .normalize import ZNormalization
 from .pad import Crop
 from .pad import Pad
 from .parameter_range import Choice
@@ -32,8 +38,8 @@ from .transform import SpatialTransform
 from .transform import Transform
 
 __all__ = [
-    "Affine", "Anisotropy", "AppliedTransform", "BiasField", "Blur", "Choice", "Compose", "Contour", "Crop", "ElasticDeformation", "Flip", "Gamma",
-    "IntensityTransform", "KeepLargestComponent", "Motion", "Noise", "OneHot", "OneOf", "Pad", "RemapLabels", "RemoveLabels", "Resample", "Resize",
-    "SequentialLabels", "SomeOf", "Spatial", "SpatialTransform", "Transform",
+    "Affine", "Anisotropy", "AppliedTransform", "BiasField", "Blur", "Choice", "Clamp", "Compose", "Contour", "Crop", "ElasticDeformation", "Flip", "Gamma",
+    "IntensityTransform", "KeepLargestComponent", "Mask", "Motion", "Noise", "Normalize", "OneHot", "OneOf", "Pad", "RemapLabels", "RemoveLabels", "Resample", "RescaleIntensity",
+    "Resize", "SequentialLabels", "SomeOf", "Spatial", "SpatialTransform", "Standardize", "Transform", "ZNormalization",
     "apply_inverse_transform", "get_inverse_transform", "get_noise_rng", "set_noise_rng",
 ]
