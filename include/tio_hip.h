@@ -649,6 +649,65 @@ int tio_intensity_mask(const void* x, void* y, int32_t dtype, int64_t n, const v
                        int64_t mask_n, double outside_value, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* Swap and HistogramStandardization (ABI 17, additive)                      */
+/* ------------------------------------------------------------------------ */
+/*
+ * Swap (transforms/intensity/swap.py:195-219 _apply_swaps, :222-258 _apply_swaps_per_instance: per swap two patch clones
+ * and two assignments, on the per-instance path through advanced-indexing gathers over index tensors).  x and y are
+ * (batch, channels, shape) of elements of `element_bytes` (1, 2, 4 or 8; no dtype is interpreted), aligned to the element
+ * only; y must not overlap x.  The swaps of a list apply one after the other to every channel; within a swap both patches
+ * are read, then A is written, then B — where the two overlap, B's write stays.  One stream-ordered copy and ONE launch
+ * whatever the number of swaps: the result is a gather from x (csrc/swap.hip has the rule and the single-writer argument).
+ *   patch        1 <= patch[a] <= shape[a]
+ *   origins_dev  device int32 [lists][s_max][2][3]: (A, B) origins; the caller keeps them inside [0, shape - patch]
+ *                (a box outside the volume is not written, and nothing outside the volume is read)
+ *   counts_dev   device int32 [lists]: the swaps of each list (at most s_max)
+ *   lists        1 (one list for the whole batch) or `batch`
+ *   s_max        0: a plain copy; origins_dev and counts_dev may then be NULL.  There is no upper limit.
+ */
+int tio_swap_patches(const void* x, void* y, int32_t element_bytes, int32_t batch, int32_t channels, const int32_t shape[3],
+                     const int32_t patch[3], const int32_t* origins_dev, const int32_t* counts_dev, int32_t lists,
+                     int32_t s_max, void* stream);
+
+/*
+ * `np.percentile(values, 100 * q)` for up to 32 fractions and EVERY batch element in one call, without the host
+ * (histogram_standardization.py:280 copies each element to the host for it, :105-106 likewise in the training).  x is
+ * (batch, channels, n_spatial); an element's values are its inside elements as float32, all channels together.  The mask
+ * is that of the statistics above — (mask_channels, n_spatial), shared by the batch elements.  A radix select over the key of
+ * tio_intensity_quantiles in four data passes of 11 / 7 / 7 / 7 bits — pass 1 one histogram per element for all ranks, the
+ * later passes one 128-bin histogram in LDS per group of ranks that share a prefix — with a one-block scan per element after
+ * each; finished on the device by numpy's rule: virtual = (100 q) / 100 * (n - 1), lower = floor(virtual), g = virtual - lower, d = upper_value -
+ * lower_value rounded to float32 (numpy subtracts in the array's dtype), then in float64 lower_value + d * g for g < 0.5,
+ * else upper_value - d * (1 - g).  A NaN among an element's values makes all its results NaN; so does n == 0.
+ *   fractions      HOST, n_fractions (1 .. 32) doubles in [0, 1]
+ *   values_dev     device float64 [batch][n_fractions], written
+ *   counts_dev     device int64 [batch], written: the inside elements of each batch element
+ *   workspace_dev  device, 16-byte aligned, tio_intensity_multi_quantiles_workspace_bytes(batch, n_fractions) bytes (0 for
+ *                  arguments the call refuses); it may hold anything
+ */
+int64_t tio_intensity_multi_quantiles_workspace_bytes(int32_t batch, int32_t n_fractions);
+int tio_intensity_multi_quantiles(const void* x, int32_t dtype, int32_t batch, int32_t channels, int64_t n_spatial,
+                                  const void* mask, int32_t mask_dtype, int32_t mask_channels, const double* fractions,
+                                  int32_t n_fractions, double* values_dev, int64_t* counts_dev, void* workspace_dev,
+                                  int64_t workspace_bytes, void* stream);
+
+/*
+ * _apply_histogram_standardization (histogram_standardization.py:276-303) for every batch element, given its percentiles
+ * on the device: a one-block kernel builds each element's table, one pass applies it.  Every step is a separately rounded
+ * float32 operation in the reference's order: the percentiles rounded to float32, `diff` of both, |diff_input| < 1e-5 ->
+ * inf, slopes by IEEE division, intercept = landmark - slope * input_landmark, bin = the number of inner edges < x
+ * (torch.bucketize, right=False), y = slope[bin] * x + intercept[bin] (a product, then a sum).  x of any tio_dtype is
+ * converted to float32 first; y has x's dtype (the reference assigns the float32 result into the image's tensor): integer
+ * dtypes by a C cast, truncating toward zero — a result outside the dtype's range is undefined, as it is in the reference.
+ *   percentiles_dev  device float64 [batch][n_landmarks] (tio_intensity_multi_quantiles' values_dev)
+ *   landmarks_dev    device float32 [n_landmarks], 2 <= n_landmarks <= 32
+ *   table_dev        device float32 [batch][3][32], workspace
+ */
+int tio_histogram_standardize(const void* x, void* y, int32_t dtype, int32_t batch, int64_t n_per_element,
+                              const double* percentiles_dev, const float* landmarks_dev, int32_t n_landmarks,
+                              float* table_dev, void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* Motion: k-space compositing                                               */
 /* ------------------------------------------------------------------------ */
 #define TIO_MAX_SEGMENTS 32

@@ -45,6 +45,7 @@ from .transforms import Pad
 from .transforms import ElasticDeformation
 from .transforms import Flip
 from .transforms import Gamma
+from .transforms import HistogramStandardization
 from .transforms import IntensityTransform
 from .transforms import Contour
 from .transforms import KeepLargestComponent
@@ -59,6 +60,7 @@ from .transforms import Mask
 from .transforms import Normalize
 from .transforms import RescaleIntensity
 from .transforms import Standardize
+from .transforms import Swap
 from .transforms import ZNormalization
 from .transforms import OneOf
 from .transforms import SomeOf
@@ -76,7 +78,7 @@ __version__ = "0.1.0"
 
 __all__ = [
     "Affine", "AffineMatrix", "Anisotropy", "AppliedTransform", "BiasField", "Blur", "Choice", "Clamp", "Compose", "Contour", "Crop", "ElasticDeformation", "Flip",
-    "Gamma", "GridSampler", "Image", "ImagesBatch", "ImagesLoader", "IntensityTransform", "KeepLargestComponent", "LabelMap", "LabelSampler", "Mask", "Motion", "Noise", "Normalize", "OneHot", "OneOf",
-    "Pad", "PatchAggregator", "PatchLocation", "PatchSampler", "Queue", "RemapLabels", "RemoveLabels", "Resample", "RescaleIntensity", "Resize", "ScalarImage", "SequentialLabels", "SomeOf", "Spatial", "SpatialTransform", "Standardize", "Subject",
+    "Gamma", "GridSampler", "HistogramStandardization", "Image", "ImagesBatch", "ImagesLoader", "IntensityTransform", "KeepLargestComponent", "LabelMap", "LabelSampler", "Mask", "Motion", "Noise", "Normalize", "OneHot", "OneOf",
+    "Pad", "PatchAggregator", "PatchLocation", "PatchSampler", "Queue", "RemapLabels", "RemoveLabels", "Resample", "RescaleIntensity", "Resize", "ScalarImage", "SequentialLabels", "SomeOf", "Spatial", "SpatialTransform", "Standardize", "Subject", "Swap",
     "SubjectsBatch", "SubjectsLoader", "Transform", "UniformSampler", "WeightedSampler", "ZNormalization", "apply_inverse_transform", "calibrate_draw_policy", "get_draw_policy", "set_draw_policy", "get_noise_plan", "set_noise_plan", "get_inverse_transform", "get_noise_rng", "get_resample_precision", "get_stencil_precision", "set_noise_rng", "set_resample_precision", "set_stencil_precision",
 ]

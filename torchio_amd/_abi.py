@@ -207,7 +207,23 @@ HIP_ONLY_PROTOTYPES = {
     ),
     "intensity_clamp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_void_p]),
     "intensity_mask": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_void_p]),
+    # Swap and HistogramStandardization (additive to ABI 17): no CPU restatement either
+    "swap_patches": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _I32x3, _I32x3, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p],
+    ),
+    "intensity_multi_quantiles_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "intensity_multi_quantiles": (
+        C.c_int,
+        [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_int32,
+         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
+    ),
+    "histogram_standardize": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p],
+    ),
 }
+MULTI_QUANTILE_MAX_FRACTIONS = 32
 
 #: every symbol include/tio_hip.h declares for libtio_hip.so
 HIP_SYMBOLS = tuple("tio_" + n for n in (*PROTOTYPES, *HIP_ONLY_PROTOTYPES))

@@ -1784,6 +1784,114 @@ class Engine:
                    mask.numel(), float(outside_value), self._stream(data))
         return out
 
+    # -- Swap and HistogramStandardization (transforms/intensity/swap.py, histogram_standardization.py) ------------------
+    def swap_patches(self, data: Tensor, locations, patch_size: Sequence[int]) -> Tensor:
+        """``_apply_swaps`` / ``_apply_swaps_per_instance`` of the reference: ``data`` is ``(B, C, I, J, K)`` of any dtype,
+        ``locations`` one list of ``((ai, aj, ak), (bi, bj, bk))`` origin pairs for the whole batch or one such list per batch
+        element, applied one after the other to every channel; where a pair's patches overlap, the second one's write stays.
+
+        One copy and one launch whatever the number of swaps; one packed upload carries the origins and the counts.
+        """
+        if data.ndim != 5:
+            raise ValueError(f"swap_patches: expected a (B, C, I, J, K) tensor, got {tuple(data.shape)}")
+        patch = [int(p) for p in patch_size]
+        shape = [int(s) for s in data.shape[2:]]
+        if len(patch) != 3 or any(p < 1 for p in patch):
+            raise ValueError(f"swap_patches: patch_size must be three positive integers, got {tuple(patch_size)}")
+        if any(p > s for p, s in zip(patch, shape, strict=True)):
+            raise ValueError(f"Patch size {tuple(patch)} cannot be larger than spatial shape {tuple(shape)}")
+        locations = list(locations)
+
+        def is_pair(entry) -> bool:  # ((ai, aj, ak), (bi, bj, bk)), as opposed to an element's list of such pairs
+            return len(entry) == 2 and all(len(origin) == 3 and not hasattr(origin[0], "__len__") for origin in entry)
+
+        shared = all(is_pair(entry) for entry in locations)
+        lists = [locations] if shared else locations
+        if not shared and len(lists) != data.shape[0]:
+            raise ValueError(f"swap_patches: {len(lists)} location lists for a batch of {data.shape[0]}")
+        s_max = max((len(entries) for entries in lists), default=0)
+        packed = torch.zeros(len(lists) * (s_max * 6 + 1), dtype=torch.int32)
+        if s_max:
+            origins = packed[: len(lists) * s_max * 6].view(len(lists), s_max, 2, 3)
+            for index, entries in enumerate(lists):
+                if entries:
+                    origins[index, : len(entries)] = torch.tensor(entries, dtype=torch.int32).view(len(entries), 2, 3)
+            limit = torch.tensor([s - p for s, p in zip(shape, patch, strict=True)], dtype=torch.int32)
+            if bool((origins < 0).any()) or bool((origins > limit).any()):
+                raise ValueError(f"swap_patches: an origin lies outside [0, shape - patch] = [0, {tuple(limit.tolist())}]")
+        packed[len(lists) * s_max * 6 :] = torch.tensor([len(entries) for entries in lists], dtype=torch.int32)
+        data = data.contiguous()
+        self._check("swap_patches", data)
+        out = torch.empty_like(data)
+        device_packed = h2d(packed, data.device) if s_max else None
+        origins_ptr = None if device_packed is None else C.c_void_p(device_packed.data_ptr())
+        counts_ptr = None if device_packed is None else C.c_void_p(device_packed.data_ptr() + len(lists) * s_max * 6 * 4)
+        self._call("swap_patches", data, _ptr(data), _ptr(out), data.element_size(), data.shape[0], data.shape[1], _i32x3(shape), _i32x3(patch),
+                   origins_ptr, counts_ptr, len(lists), s_max, self._stream(data))
+        return out
+
+    def _batch_and_mask(self, data: Tensor, mask: Tensor | None, what: str) -> tuple[Tensor, Tensor | None]:
+        if data.ndim != 5:
+            raise ValueError(f"{what}: expected a (B, C, I, J, K) tensor, got {tuple(data.shape)}")
+        data = data.contiguous()
+        if mask is not None:
+            if mask.ndim != 4 or tuple(mask.shape[1:]) != tuple(data.shape[2:]) or mask.shape[0] not in (1, data.shape[1]):
+                raise ValueError(f"{what}: a mask of shape {tuple(mask.shape)} does not broadcast over data of shape {tuple(data.shape)}")
+            mask = mask.contiguous()
+            if mask.dtype == torch.bool:
+                mask = mask.view(torch.uint8)
+        self._check(what, data, mask)
+        return data, mask
+
+    def intensity_multi_quantiles(self, data: Tensor, fractions: Sequence[float], mask: Tensor | None = None) -> tuple[Tensor, Tensor]:
+        """``np.percentile(values, [100 * q for q in fractions])`` for every batch element of ``data`` ``(B, C, I, J, K)``,
+        ``values`` being the element's voxels (all channels) inside ``mask`` as float32: ``(percentiles, counts)``, a float64
+        ``(B, len(fractions))`` and an int64 ``(B,)`` tensor ON THE DEVICE — nothing is read back, nothing synchronises.
+
+        ``mask``: ``(1 or C, I, J, K)`` on the device, any dtype, nonzero = inside, the same for every element.  Up to 32
+        fractions.  A NaN inside an element, or nothing inside, makes its percentiles NaN.
+        """
+        fractions = [float(q) for q in fractions]
+        if not 1 <= len(fractions) <= _abi.MULTI_QUANTILE_MAX_FRACTIONS:
+            raise ValueError(f"intensity_multi_quantiles: 1 to {_abi.MULTI_QUANTILE_MAX_FRACTIONS} fractions, got {len(fractions)}")
+        for q in fractions:
+            if not 0 <= q <= 1:
+                raise ValueError(f"Only values 0 <= q <= 1 are supported, but got {q!r}")
+        data, mask = self._batch_and_mask(data, mask, "intensity_multi_quantiles")
+        batch = data.shape[0]
+        values = torch.empty((batch, len(fractions)), dtype=torch.float64, device=data.device)
+        counts = torch.empty(batch, dtype=torch.int64, device=data.device)
+        nbytes = int(self._fn["intensity_multi_quantiles_workspace_bytes"](batch, len(fractions)))
+        workspace = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=data.device)
+        spatial = data.shape[2] * data.shape[3] * data.shape[4]
+        self._call("intensity_multi_quantiles", data, _ptr(data), dtype_code(data.dtype), batch, data.shape[1], spatial, _ptr(mask),
+                   0 if mask is None else dtype_code(mask.dtype), 0 if mask is None else mask.shape[0],
+                   (C.c_double * len(fractions))(*fractions), len(fractions), _ptr(values), _ptr(counts), _ptr(workspace), nbytes,
+                   self._stream(data))
+        return values, counts
+
+    def histogram_standardize(self, data: Tensor, landmarks: Tensor, quantiles: Sequence[float]) -> Tensor:
+        """``_apply_histogram_standardization`` of the reference for every element of ``data`` ``(B, C, I, J, K)``: the
+        element's percentiles at ``quantiles`` (``intensity_multi_quantiles``), the piecewise-linear map onto ``landmarks`` (a
+        float32 tensor with one value per quantile), the result in ``data``'s dtype.  No read-back, no synchronisation.
+        """
+        if landmarks.ndim != 1 or landmarks.numel() != len(quantiles):
+            raise ValueError(f"histogram_standardize: {landmarks.numel()} landmarks for {len(quantiles)} quantiles")
+        if landmarks.numel() < 2:
+            raise ValueError("histogram_standardize: at least 2 landmarks")
+        percentiles, _ = self.intensity_multi_quantiles(data, quantiles)
+        data = data.contiguous()
+        landmarks = landmarks.to(torch.float32).contiguous()
+        if landmarks.device != data.device:
+            landmarks = h2d(landmarks, data.device)
+        self._check("histogram_standardize", landmarks)
+        batch = data.shape[0]
+        out = torch.empty_like(data)
+        table = torch.empty((max(batch, 1), 3, _abi.MULTI_QUANTILE_MAX_FRACTIONS), dtype=torch.float32, device=data.device)
+        self._call("histogram_standardize", data, _ptr(data), _ptr(out), dtype_code(data.dtype), batch, data.numel() // batch if batch else 0,
+                   _ptr(percentiles), _ptr(landmarks), landmarks.numel(), _ptr(table), self._stream(data))
+        return out
+
     def kspace_segment_mix(self, segments: Sequence[Tensor], bounds: Sequence[int], out_dtype: torch.dtype,
                            active: Tensor | None = None) -> Tensor:
         """Motion's k-space composite (motion.py:334-372) of float32 ``(B, C, I, J, K)`` images.
