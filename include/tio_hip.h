@@ -708,6 +708,60 @@ int tio_histogram_standardize(const void* x, void* y, int32_t dtype, int32_t bat
                               float* table_dev, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* Ghosting and Spike (ABI 17, additive): csrc/kspace_artefacts.hip          */
+/* ------------------------------------------------------------------------ */
+/*
+ * Both entries below that take `tables_dev` read the SAME table: device float32 [I + J + K][2], for each spatial axis in
+ * turn (cos, sin)(2 pi r / S), r = 0 .. S-1, S the axis' length — evaluated in double and rounded once to float32 by the
+ * caller, 8-byte aligned.  Arithmetic is float32; x of any tio_dtype is converted on load, y has x's dtype (the reference's
+ * `.float()` / `.to(dtype)`: integers truncate toward zero) and must not overlap x.  Data is aligned to its element only.
+ * Every axis has at most 32768 voxels, a volume fewer than 2^31, batch * channels at most 65535 (more:
+ * TIO_ERR_UNSUPPORTED_CONFIG).  `active_dev`: device uint8 [batch] or NULL (all active).  An inactive element, one with
+ * an empty list, or one with zero strength / intensity comes out as an exact copy of its input, bit for bit.
+ */
+
+/*
+ * Ghosting (transforms/intensity/ghosting.py:218-277 _add_ghosting, :149-215 _add_ghosting_per_element: fftn, fftshift, a
+ * mask along one axis, ifftshift, ifftn, real part).  For every line along the element's axis (length S)
+ *     out[i] = x[i] - (strength / S) * sum_{f in Z} ( cos(2 pi f i / S) A_f + sin(2 pi f i / S) B_f ),
+ *     A_f = sum_i' cos(2 pi f i' / S) x[i'],   B_f = sum_i' sin(2 pi f i' / S) x[i']
+ * with Z the UNSHIFTED frequencies of the scaled planes (shifted index u -> (u - S/2) mod S, S/2 rounded down); a
+ * frequency listed twice counts twice.  One launch per axis in `axes_mask`; no transposed copy for any axis.
+ *   axes_mask     bit a set: some element's axis is a.  An element whose axis has no bit is NOT WRITTEN.
+ *   params_dev    device int32 [params_words]: per batch element {axis, count, offset, strength as float32 bits}, then
+ *                 the frequencies; `offset` is the word index of the element's first frequency.  A list that leaves
+ *                 [4 * batch, params_words) makes its element a copy; a frequency outside [0, S) contributes nothing.
+ *   max_count     no element uses more than this many frequencies (longer lists are cut); decides the LDS layout
+ * An axis longer than LDS holds an accumulator line for (about 9600 voxels): TIO_ERR_UNSUPPORTED_CONFIG.
+ */
+int tio_kspace_ghost_lines(const void* x, void* y, int32_t dtype, int32_t batch, int32_t channels, const int32_t shape[3],
+                           int32_t axes_mask, const int32_t* params_dev, int32_t params_words, int32_t max_count,
+                           const float* tables_dev, const uint8_t* active_dev, void* stream);
+
+/*
+ * `spectrum.abs().amax(dim=(-3, -2, -1))` (transforms/intensity/spike.py:152, :201) of a spectrum the caller computed: z is
+ * (rows, n) interleaved complex64 on the device, 8-byte aligned; out_dev receives `rows` float32 maxima of |z| (0 for
+ * n == 0).  The call clears and writes out_dev itself, the caller prepares nothing; every element is read once.
+ * |z| = sqrt(re^2 + im^2) in float32, within 2 ulp of hypot.  CONTRACT: finite input with |re|, |im| < 1.8e19 (the squares
+ * must not overflow; a NaN is ignored, not propagated).  rows <= 65535.
+ */
+int tio_complex_abs_max(const void* z, int64_t rows, int64_t n, float* out_dev, void* stream);
+
+/*
+ * Spike (transforms/intensity/spike.py:124-162 _add_spikes, :165-223 _add_spikes_per_instance: fftn, fftshift, peak * intensity
+ * added at a few points, ifftshift, ifftn, real part):
+ *     out[i, j, k] = x[i, j, k] + (peak * intensity / (I J K)) * sum_p cos 2 pi (f_p0 i / I + f_p1 j / J + f_p2 k / K)
+ * with (f_p0, f_p1, f_p2) the UNSHIFTED frequencies of point p; a point listed twice counts twice.  One pass, 16-byte
+ * accesses where x and y share their phase inside 16 bytes, single elements otherwise.
+ *   params_dev    device int32 [params_words]: per batch element {count, offset, intensity as float32 bits, 0}, then the
+ *                 triples; `offset` is the word index of the element's first triple.  Checked like the ghost lists.
+ *   peaks_dev     device float32 [batch * channels] (tio_complex_abs_max); read on the device only
+ */
+int tio_kspace_add_spikes(const void* x, void* y, int32_t dtype, int32_t batch, int32_t channels, const int32_t shape[3],
+                          const int32_t* params_dev, int32_t params_words, int32_t max_count, const float* tables_dev,
+                          const float* peaks_dev, const uint8_t* active_dev, void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* Motion: k-space compositing                                               */
 /* ------------------------------------------------------------------------ */
 #define TIO_MAX_SEGMENTS 32

@@ -64,12 +64,11 @@ def install_alias() -> None:
 
         return type(name, (torchio_amd.transforms.Transform,), {"__init__": __init__, "forward": skip, "make_params": skip})
 
-    for missing in ("Ghosting", "Spike"):
-        if not hasattr(torchio_amd, missing):
-            setattr(torchio_amd, missing, _placeholder(missing))
-    # Swap exists in the package, but this run computes on the CPU oracle, which has no counterpart of tio_swap_patches (the
-    # HIP-only entry points are checked on the GPU, tests/test_gpu_swap_histogram.py): the placeholder stays whatever is exported
-    torchio_amd.Swap = _placeholder("Swap")
+    # Ghosting, Spike and Swap exist in the package, but this run computes on the CPU oracle, which has no counterpart of
+    # their HIP-only entry points (those are checked on the GPU, tests/test_gpu_kspace_artefacts.py and
+    # tests/test_gpu_swap_histogram.py): the placeholders stay whatever is exported
+    for hip_only in ("Ghosting", "Spike", "Swap"):
+        setattr(torchio_amd, hip_only, _placeholder(hip_only))
 
     # the reference keeps its spatial transforms in a package (torchio.transforms.spatial.spatial); private helpers
     # with no counterpart here (the sampling grid is never materialised ...) resolve to a stub that raises when called

@@ -45,6 +45,7 @@ from .transforms import Pad
 from .transforms import ElasticDeformation
 from .transforms import Flip
 from .transforms import Gamma
+from .transforms import Ghosting
 from .transforms import HistogramStandardization
 from .transforms import IntensityTransform
 from .transforms import Contour
@@ -60,6 +61,7 @@ from .transforms import Mask
 from .transforms import Normalize
 from .transforms import RescaleIntensity
 from .transforms import Standardize
+from .transforms import Spike
 from .transforms import Swap
 from .transforms import ZNormalization
 from .transforms import OneOf
@@ -78,7 +80,7 @@ __version__ = "0.1.0"
 
 __all__ = [
     "Affine", "AffineMatrix", "Anisotropy", "AppliedTransform", "BiasField", "Blur", "Choice", "Clamp", "Compose", "Contour", "Crop", "ElasticDeformation", "Flip",
-    "Gamma", "GridSampler", "HistogramStandardization", "Image", "ImagesBatch", "ImagesLoader", "IntensityTransform", "KeepLargestComponent", "LabelMap", "LabelSampler", "Mask", "Motion", "Noise", "Normalize", "OneHot", "OneOf",
-    "Pad", "PatchAggregator", "PatchLocation", "PatchSampler", "Queue", "RemapLabels", "RemoveLabels", "Resample", "RescaleIntensity", "Resize", "ScalarImage", "SequentialLabels", "SomeOf", "Spatial", "SpatialTransform", "Standardize", "Subject", "Swap",
+    "Gamma", "Ghosting", "GridSampler", "HistogramStandardization", "Image", "ImagesBatch", "ImagesLoader", "IntensityTransform", "KeepLargestComponent", "LabelMap", "LabelSampler", "Mask", "Motion", "Noise", "Normalize", "OneHot", "OneOf",
+    "Pad", "PatchAggregator", "PatchLocation", "PatchSampler", "Queue", "RemapLabels", "RemoveLabels", "Resample", "RescaleIntensity", "Resize", "ScalarImage", "SequentialLabels", "SomeOf", "Spatial", "SpatialTransform", "Spike", "Standardize", "Subject", "Swap",
     "SubjectsBatch", "SubjectsLoader", "Transform", "UniformSampler", "WeightedSampler", "ZNormalization", "apply_inverse_transform", "calibrate_draw_policy", "get_draw_policy", "set_draw_policy", "get_noise_plan", "set_noise_plan", "get_inverse_transform", "get_noise_rng", "get_resample_precision", "get_stencil_precision", "set_noise_rng", "set_resample_precision", "set_stencil_precision",
 ]

@@ -222,6 +222,18 @@ HIP_ONLY_PROTOTYPES = {
         C.c_int,
         [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p],
     ),
+    # Ghosting and Spike (additive to ABI 17): no CPU restatement either
+    "kspace_ghost_lines": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _I32x3, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+         C.c_void_p, C.c_void_p],
+    ),
+    "complex_abs_max": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "kspace_add_spikes": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _I32x3, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+         C.c_void_p, C.c_void_p],
+    ),
 }
 MULTI_QUANTILE_MAX_FRACTIONS = 32
 

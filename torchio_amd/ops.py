@@ -18,6 +18,7 @@ import threading
 import types
 from collections.abc import Sequence
 
+import numpy as np
 import torch
 from torch import Tensor
 
@@ -1890,6 +1891,164 @@ class Engine:
         table = torch.empty((max(batch, 1), 3, _abi.MULTI_QUANTILE_MAX_FRACTIONS), dtype=torch.float32, device=data.device)
         self._call("histogram_standardize", data, _ptr(data), _ptr(out), dtype_code(data.dtype), batch, data.numel() // batch if batch else 0,
                    _ptr(percentiles), _ptr(landmarks), landmarks.numel(), _ptr(table), self._stream(data))
+        return out
+
+    # -- Ghosting and Spike (transforms/intensity/ghosting.py, spike.py) ---------------------------------------------------
+    def _phase_tables(self, shape: Sequence[int], device) -> Tensor:
+        """``(I + J + K, 2)`` float32 on *device*: per axis ``(cos, sin)(2 pi r / S)``, evaluated in float64 on the host and
+        rounded once (built once per shape)."""
+        cache = self.__dict__.setdefault("_phase_table_cache", {})
+        key = (tuple(int(s) for s in shape), str(device))
+        table = cache.get(key)
+        if table is None:
+            rows = []
+            for size in key[0]:
+                angle = 2.0 * np.pi * np.arange(size, dtype=np.float64) / max(size, 1)
+                rows.append(np.stack([np.cos(angle), np.sin(angle)], axis=1))
+            host = torch.from_numpy(np.concatenate(rows).astype(np.float32))
+            if len(cache) >= 8:
+                cache.clear()
+            table = cache[key] = h2d(host, device)
+        return table
+
+    @staticmethod
+    def _per_element(value, batch: int, what: str) -> list:
+        """A scalar for the whole batch, or one entry per element."""
+        if isinstance(value, (list, tuple)):
+            if len(value) != batch:
+                raise ValueError(f"{what}: {len(value)} entries for a batch of {batch}")
+            return list(value)
+        return [value] * batch
+
+    @staticmethod
+    def _per_element_lists(lists, batch: int, what: str, item_is_sequence: bool) -> list[list]:
+        """One list of items for the whole batch, or one such list per element (an item: an integer, or a triple when
+        ``item_is_sequence``).  An empty entry is an element's empty list."""
+        lists = list(lists)
+
+        def is_element_list(entry) -> bool:
+            if not isinstance(entry, (list, tuple)):
+                return False
+            return not item_is_sequence or len(entry) == 0 or isinstance(entry[0], (list, tuple))
+
+        if not any(is_element_list(entry) for entry in lists):
+            return [lists] * batch
+        if len(lists) != batch or not all(is_element_list(entry) for entry in lists):
+            raise ValueError(f"{what}: {len(lists)} lists for a batch of {batch}")
+        return [list(entry) for entry in lists]
+
+    def ghost_lines(self, data: Tensor, axes, strengths, frequency_lists, active: Tensor | None = None) -> Tensor:
+        """``_add_ghosting`` / ``_add_ghosting_per_element`` of the reference in image space: along ``axes[b]`` every line of
+        element ``b`` loses ``strengths[b]`` of its components at the UNSHIFTED frequencies ``frequency_lists[b]`` (the
+        k-space planes the reference scales by ``1 - strength``).  ``axes`` / ``strengths``: one value or one per element;
+        ``frequency_lists``: one list of integers or one list per element.  ``data`` is ``(B, C, I, J, K)`` of any dtype; the
+        result has its dtype.  Elements with ``active[b] == 0``, an empty list or zero strength are exact copies.
+
+        One reduction and one update per line, no FFT, no complex volume; one packed upload carries every list.
+        """
+        if data.ndim != 5:
+            raise ValueError(f"ghost_lines: expected a (B, C, I, J, K) tensor, got {tuple(data.shape)}")
+        batch, shape = int(data.shape[0]), [int(s) for s in data.shape[2:]]
+        axes = [int(a) for a in self._per_element(axes, batch, "ghost_lines: axes")]
+        strengths = [float(s) for s in self._per_element(strengths, batch, "ghost_lines: strengths")]
+        lists = self._per_element_lists(frequency_lists, batch, "ghost_lines: frequency_lists", False)
+        for axis, frequencies in zip(axes, lists, strict=True):
+            if axis not in (0, 1, 2):
+                raise ValueError(f"ghost_lines: axis {axis} (0, 1 or 2)")
+            if any(int(f) != f or not 0 <= f < max(shape[axis], 1) for f in frequencies):
+                raise ValueError(f"ghost_lines: a frequency outside [0, {shape[axis]}) along axis {axis}")
+        flags = self._flags(active, batch, "ghost_lines: active")
+        data = data.contiguous()
+        self._check("ghost_lines", data, flags)
+        out = torch.empty_like(data)
+        if data.numel() == 0:
+            return out
+        words = [0] * (4 * batch)
+        for b, (axis, strength, frequencies) in enumerate(zip(axes, strengths, lists, strict=True)):
+            words[4 * b : 4 * b + 4] = [axis, len(frequencies), len(words), int(np.float32(strength).view(np.int32))]
+            words.extend(int(f) for f in frequencies)
+        params = h2d(torch.tensor(words, dtype=torch.int32), data.device)
+        mask = 0
+        for axis in axes:
+            mask |= 1 << axis
+        tables = self._phase_tables(shape, data.device)
+        self._call("kspace_ghost_lines", data, _ptr(data), _ptr(out), dtype_code(data.dtype), batch, data.shape[1], _i32x3(shape), mask,
+                   _ptr(params), len(words), max(len(f) for f in lists), _ptr(tables), _ptr(flags), self._stream(data))
+        return out
+
+    #: bytes of half spectrum (the rfftn result) that `spectrum_peak` holds at a time; one volume's always fits
+    RFFTN_CHUNK_BYTES = 256 << 20
+
+    def complex_abs_max(self, spectrum: Tensor, out: Tensor | None = None) -> Tensor:
+        """``spectrum.abs().amax(1)`` of a contiguous complex64 ``(rows, n)`` device tensor: ``rows`` float32 maxima, each
+        element read once (``tio_complex_abs_max``; finite input).  ``out``: a float32 ``(rows,)`` tensor to write into."""
+        if spectrum.ndim != 2 or spectrum.dtype != torch.complex64:
+            raise ValueError(f"complex_abs_max: expected a complex64 (rows, n) tensor, got {spectrum.dtype} {tuple(spectrum.shape)}")
+        spectrum = spectrum.contiguous()
+        self._check("complex_abs_max", spectrum, out)
+        rows, n = spectrum.shape
+        if out is None:
+            out = torch.empty(rows, dtype=torch.float32, device=spectrum.device)
+        elif out.dtype != torch.float32 or out.numel() != rows or not out.is_contiguous():
+            raise ValueError(f"complex_abs_max: out must be {rows} contiguous float32 values")
+        self._call("complex_abs_max", spectrum, _ptr(spectrum), rows, n, _ptr(out), self._stream(spectrum))
+        return out
+
+    def spectrum_peak(self, data: Tensor) -> Tensor:
+        """``fftn(data.float()).abs().amax`` over the spatial axes of ``(B, C, I, J, K)`` data: ``(B * C,)`` float32 ON THE
+        DEVICE.  The input is real, so the half spectrum of ``rfftn`` holds the same maximum; it is taken a few volumes at a
+        time (at most ``RFFTN_CHUNK_BYTES`` of spectrum, one volume at least) and reduced by ``complex_abs_max`` in one read.
+        The library FFT of this family lives here only.
+        """
+        if data.ndim != 5:
+            raise ValueError(f"spectrum_peak: expected a (B, C, I, J, K) tensor, got {tuple(data.shape)}")
+        self._check("spectrum_peak", data)
+        volumes = int(data.shape[0] * data.shape[1])
+        peaks = torch.empty(volumes, dtype=torch.float32, device=data.device)
+        if data.numel() == 0:
+            return peaks.zero_()
+        spatial = tuple(int(s) for s in data.shape[2:])
+        flat = data.reshape(volumes, *spatial)
+        per_volume = spatial[0] * spatial[1] * (spatial[2] // 2 + 1) * 8
+        step = max(1, self.RFFTN_CHUNK_BYTES // per_volume)
+        for start in range(0, volumes, step):
+            spectrum = torch.fft.rfftn(flat[start : start + step].float(), dim=(-3, -2, -1))
+            self.complex_abs_max(spectrum.reshape(spectrum.shape[0], -1), peaks[start : start + step])
+        return peaks
+
+    def add_spikes(self, data: Tensor, frequency_lists, intensities, peaks: Tensor, active: Tensor | None = None) -> Tensor:
+        """``_add_spikes`` / ``_add_spikes_per_instance`` of the reference in image space: element ``b`` gains
+        ``peaks[b, c] * intensities[b] / (I J K)`` times the sum of the plane waves at the UNSHIFTED frequency triples
+        ``frequency_lists[b]`` (a triple listed twice counts twice).  ``frequency_lists``: one list of triples or one list per
+        element; ``intensities``: one value or one per element; ``peaks``: the ``(B * C,)`` float32 device tensor of
+        ``spectrum_peak`` — never read back.  Elements with ``active[b] == 0``, no triple or zero intensity are exact copies.
+        """
+        if data.ndim != 5:
+            raise ValueError(f"add_spikes: expected a (B, C, I, J, K) tensor, got {tuple(data.shape)}")
+        batch, shape = int(data.shape[0]), [int(s) for s in data.shape[2:]]
+        intensities = [float(s) for s in self._per_element(intensities, batch, "add_spikes: intensities")]
+        lists = self._per_element_lists(frequency_lists, batch, "add_spikes: frequency_lists", True)
+        for triples in lists:
+            for triple in triples:
+                if len(triple) != 3 or any(int(f) != f or not 0 <= f < max(s, 1) for f, s in zip(triple, shape, strict=True)):
+                    raise ValueError(f"add_spikes: {tuple(triple)} is not a frequency triple inside {tuple(shape)}")
+        if peaks.dtype != torch.float32 or peaks.numel() != batch * data.shape[1]:
+            raise ValueError(f"add_spikes: peaks must hold {batch * data.shape[1]} float32 values, got {peaks.numel()} of {peaks.dtype}")
+        flags = self._flags(active, batch, "add_spikes: active")
+        data, peaks = data.contiguous(), peaks.contiguous()
+        self._check("add_spikes", data, peaks, flags)
+        out = torch.empty_like(data)
+        if data.numel() == 0:
+            return out
+        words = [0] * (4 * batch)
+        for b, (intensity, triples) in enumerate(zip(intensities, lists, strict=True)):
+            words[4 * b : 4 * b + 4] = [len(triples), len(words), int(np.float32(intensity).view(np.int32)), 0]
+            for triple in triples:
+                words.extend(int(f) for f in triple)
+        params = h2d(torch.tensor(words, dtype=torch.int32), data.device)
+        tables = self._phase_tables(shape, data.device)
+        self._call("kspace_add_spikes", data, _ptr(data), _ptr(out), dtype_code(data.dtype), batch, data.shape[1], _i32x3(shape), _ptr(params),
+                   len(words), max(len(t) for t in lists), _ptr(tables), _ptr(peaks), _ptr(flags), self._stream(data))
         return out
 
     def kspace_segment_mix(self, segments: Sequence[Tensor], bounds: Sequence[int], out_dtype: torch.dtype,

@@ -6,6 +6,7 @@ from .compose import OneOf
 from .compose import SomeOf
 from .flip import Flip
 from .gamma import Gamma
+from .ghosting import Ghosting
 from .histogram_standardization import HistogramStandardization
 from .inverse import apply_inverse_transform
 from .inverse import get_inverse_transform
@@ -33,6 +34,7 @@ from .spatial import Affine
 from .spatial import ElasticDeformation
 from .spatial import Resample
 from .spatial import Spatial
+from .spike import Spike
 from .swap import Swap
 from .transform import AppliedTransform
 from .transform import IntensityTransform
@@ -40,8 +42,8 @@ from .transform import SpatialTransform
 from .transform import Transform
 
 __all__ = [
-    "Affine", "Anisotropy", "AppliedTransform", "BiasField", "Blur", "Choice", "Clamp", "Compose", "Contour", "Crop", "ElasticDeformation", "Flip", "Gamma",
+    "Affine", "Anisotropy", "AppliedTransform", "BiasField", "Blur", "Choice", "Clamp", "Compose", "Contour", "Crop", "ElasticDeformation", "Flip", "Gamma", "Ghosting",
     "HistogramStandardization", "IntensityTransform", "KeepLargestComponent", "Mask", "Motion", "Noise", "Normalize", "OneHot", "OneOf", "Pad", "RemapLabels", "RemoveLabels", "Resample", "RescaleIntensity",
-    "Resize", "SequentialLabels", "SomeOf", "Spatial", "SpatialTransform", "Standardize", "Swap", "Transform", "ZNormalization",
+    "Resize", "SequentialLabels", "SomeOf", "Spatial", "SpatialTransform", "Spike", "Standardize", "Swap", "Transform", "ZNormalization",
     "apply_inverse_transform", "get_inverse_transform", "get_noise_rng", "set_noise_rng",
 ]
