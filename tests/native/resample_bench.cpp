@@ -6,7 +6,7 @@
 //
 // perf   : 256^3-class float32 volumes, per-element affine (±10°, 0.9-1.1, ±5 vox) and
 //          7^3 elastic control points (±7.5 mm), the bench.py workload geometry;
-//          every path (gather, tile variants) timed and checked against gather.
+//          every path (gather, the brick and planned kernels) timed and checked against gather.
 // parity : awkward shapes / dtypes / fills / flags, every path vs the CPU oracle.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -170,23 +170,22 @@ static void fill_random(std::vector<uint8_t>& buf, int dtype, size_t n) {
 }
 
 static double g_hint_from = 12.0;
-struct Paths { const char* name; const char* path; const char* variant; int precision; const char* kernel; const char* v2; };
+struct Paths { const char* name; const char* path; int precision; const char* kernel; const char* v2; };
 static const Paths kPaths[] = {
-    {"gather", "gather", "0", 0, nullptr, nullptr}, {"tile16x16x16", "tile", "0", 0, nullptr, nullptr}, {"tile16x8x32", "tile", "1", 0, nullptr, nullptr},
-    {"tile8x8x32", "tile", "2", 0, nullptr, nullptr}, {"tile8x16x32w8", "tile", "3", 0, nullptr, nullptr}, {"tile8x16x16", "tile", "4", 0, nullptr, nullptr},
+    {"gather", "gather", 0, nullptr, nullptr}, {"tile16x16x16", "tile", 0, nullptr, nullptr},
     // TIO_PRECISION_FAST (float32 trilinear launches only; held to 1e-4 OF THE INTENSITY RANGE, its contract — it cannot meet the
     // per-voxel bar on white noise: resample_lean_exact.hpp): the planned bricks of resample_fast.hpp (forced here whatever the
     // size) and the brick kernel's FAST instantiation (small launches, A/B)
-    {"fast", "tile", "0", 1, "planned", "0"}, {"fast-brick", "tile", "0", 1, "brick", "0"},
+    {"fast", "tile", 1, "planned", "0"}, {"fast-brick", "tile", 1, "brick", "0"},
     // round 3 A/B: the general planned kernel for a single-channel image too (TIO_PLANNED_LEAN=0)
-    {"fast-general", "tile", "0", 1, "planned", "nolean"},
+    {"fast-general", "tile", 1, "planned", "nolean"},
     // round 5 (resample_lean_exact.hpp): the lean planned kernel with the reference's own coordinates, forced whatever the size.
     // "lean-exact" = TIO_PRECISION_EXACT, ATen's interpolation order: compared BIT FOR BIT; "tight" = TIO_PRECISION_TIGHT, fused
     // lerps: held per voxel to |d| <= 1e-4 max(|ref|, 1e-3 range), no exempt voxel.  "-seq": the box requested before phase A
     // (TIO_LEAN_INTERLEAVE=0, A/B of the interleaved DMA issue)
-    {"lean-exact", "tile", "0", 0, "planned", "lean-exact"}, {"tight", "tile", "0", 2, "planned", "0"},
-    {"lean-exact-seq", "tile", "0", 0, "planned", "lean-exact-seq"}, {"tight-seq", "tile", "0", 2, "planned", "seq"},
-    {"tight-dma1st", "tile", "0", 2, "planned", "dmafirst"}};
+    {"lean-exact", "tile", 0, "planned", "lean-exact"}, {"tight", "tile", 2, "planned", "0"},
+    {"lean-exact-seq", "tile", 0, "planned", "lean-exact-seq"}, {"tight-seq", "tile", 2, "planned", "seq"},
+    {"tight-dma1st", "tile", 2, "planned", "dmafirst"}};
 
 // --ablate 64: the lean kernel overwrites the first output row of every brick with its block's shader-clock stamps
 // (resample_fast.hpp); medians of the phases, and how many blocks of a CU were alive together
@@ -340,7 +339,6 @@ static int run_case(Case& cs, int reps, bool check_oracle, bool time_it) {
   for (size_t p = 0; p < sizeof(kPaths) / sizeof(kPaths[0]); p++) {
     if (p != 0 && !g_path_filter.empty() && std::string(kPaths[p].name).find(g_path_filter) == std::string::npos) continue;
     setenv("TIO_RESAMPLE_PATH", kPaths[p].path, 1);
-    setenv("TIO_TILE_VARIANT", kPaths[p].variant, 1);
     if (kPaths[p].kernel) setenv("TIO_FAST_KERNEL", kPaths[p].kernel, 1); else unsetenv("TIO_FAST_KERNEL");
     const std::string mix = kPaths[p].v2 ? kPaths[p].v2 : "";
     setenv("TIO_PLANNED_LEAN", mix == "nolean" ? "0" : "1", 1);
@@ -466,7 +464,6 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--case") && i + 1 < argc) g_case_filter = argv[++i];
     else if (!strcmp(argv[i], "--path") && i + 1 < argc) g_path_filter = argv[++i];
     else if (!strcmp(argv[i], "--ablate") && i + 1 < argc) setenv("TIO_TILE_ABLATE", argv[++i], 1);
-    else if (!strcmp(argv[i], "--lds") && i + 1 < argc) setenv("TIO_TILE_LDS_FLOATS", argv[++i], 1);
     else if (!strcmp(argv[i], "--hint-from") && i + 1 < argc) g_hint_from = atof(argv[++i]);  // geometry cases: TIO_GEOM_LARGE_BOXES from this many degrees (< 0: never)
   }
   if (tio_device_count() < 1) { fprintf(stderr, "no HIP device\n"); return 2; }
@@ -661,7 +658,7 @@ int main(int argc, char** argv) {
   }
   if (cases == "geometry") {
     // round 6: the same launch over geometries that change the size of a brick's input box — a pure translation (the
-    // smallest box a brick can have: what more resident blocks per CU would buy, with --lds), the bench's ranges, and
+    // smallest box a brick can have), the bench's ranges, and
     // rotations beyond them (boxes beyond the tile: what the multi-pass form is for)
     const double degs[] = {0.0, 10.0, 15.0, 20.0, 30.0, 45.0};
     for (double deg : degs) {

@@ -29,7 +29,7 @@ PLAN_HEADER_INTS, DESC_INTS, PASS_INTS, PASSES_PER_BRICK = 16, 16, 8, 4  # resam
 
 #: every switch that takes part in the route choice: cleared for each case, then the case's own are set
 SWITCHES = ("TIO_FAST_KERNEL", "TIO_EXACT_LEAN", "TIO_EXACT_PLAN", "TIO_PLANNED_LEAN", "TIO_LEAN_MULTI", "TIO_RESAMPLE_PATH",
-            "TIO_RESAMPLE_EXACT", "TIO_TILE_VARIANT", "TIO_TILE_ABLATE", "TIO_TILE_LDS_FLOATS", "TIO_NEAREST_KERNEL")
+            "TIO_RESAMPLE_EXACT", "TIO_TILE_ABLATE", "TIO_NEAREST_KERNEL")
 
 PRECISIONS = {"exact": _abi.PRECISION_EXACT, "fast": _abi.PRECISION_FAST, "tight": _abi.PRECISION_TIGHT}
 FLAGS = {"none": 0, "large": _abi.GEOM_LARGE_BOXES, "mostly_large": _abi.GEOM_MOSTLY_LARGE_BOXES}

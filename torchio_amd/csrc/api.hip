@@ -45,13 +45,10 @@ static const EnvSwitches* parse_env() {
   e->nearest_kernel = num("TIO_NEAREST_KERNEL", 1) != 0;
   if (const char* v = getenv("TIO_NEAREST_EPS")) { e->has_nearest_eps = 1; e->nearest_eps = static_cast<float>(atof(v)); }
   if (const char* v = getenv("TIO_RESAMPLE_PATH")) e->resample_path = strcmp(v, "gather") == 0 ? 1 : (strcmp(v, "tile") == 0 ? 2 : 0);
-  e->tile_variant = num("TIO_TILE_VARIANT", 0);
-  e->tile_lds_floats = num("TIO_TILE_LDS_FLOATS", 0);
   e->tile_ablate = num("TIO_TILE_ABLATE", 0);
   e->resample_exact = getenv("TIO_RESAMPLE_EXACT") != nullptr;
   if (const char* v = getenv("TIO_FAST_KERNEL")) e->fast_kernel = strcmp(v, "brick") == 0 ? 1 : (strcmp(v, "planned") == 0 ? 2 : 0);
   e->planned_lean = num("TIO_PLANNED_LEAN", 1) != 0;
-  e->dma_packed = num("TIO_DMA_PACKED", 1) != 0;
   e->exact_plan = num("TIO_EXACT_PLAN", -1);
   e->exact_lean = num("TIO_EXACT_LEAN", -1);
   e->lean_interleave = num("TIO_LEAN_INTERLEAVE", 1);
@@ -59,13 +56,9 @@ static const EnvSwitches* parse_env() {
   e->nearest_exact = num("TIO_NEAREST_EXACT", 1);
   e->lean_pair = num("TIO_LEAN_PAIR", 1);
   e->lean_label = num("TIO_LEAN_LABEL", 1);
-  e->nearest_lds = num("TIO_NEAREST_LDS", -1);
   e->fast_fill_recheck = num("TIO_FAST_FILL_RECHECK", 1) != 0;
   e->conv_no_fuse = getenv("TIO_CONV_NO_FUSE") != nullptr;
   e->conv_ring = getenv("TIO_CONV_RING") != nullptr;
-  e->march_segs = num("TIO_MARCH_SEGS", 0);
-  e->march_order = num("TIO_MARCH_ORDER", -1);
-  e->min_blocks = num("TIO_MIN_BLOCKS", 0);
   return e;
 }
 

@@ -27,17 +27,13 @@ struct EnvSwitches {
   int has_nearest_eps = 0;       // TIO_NEAREST_EPS (calibration runs only)
   float nearest_eps = 0.0f;
   int resample_path = 0;         // TIO_RESAMPLE_PATH: 0 unset, 1 gather, 2 tile
-  int tile_variant = 0;          // TIO_TILE_VARIANT
-  int tile_lds_floats = 0;       // TIO_TILE_LDS_FLOATS
-  int tile_ablate = 0;           // TIO_TILE_ABLATE (instrumented instantiations only)
+  int tile_ablate = 0;           // TIO_TILE_ABLATE (the planned lean kernel's instrumented instantiation only)
   int resample_exact = 0;        // TIO_RESAMPLE_EXACT set: never the FAST kernels, and TIGHT launches interpolate in ATen's order (bit-exact)
   int fast_kernel = 0;           // TIO_FAST_KERNEL: 0 unset, 1 brick, 2 planned
   int planned_lean = 1;          // TIO_PLANNED_LEAN
-  int dma_packed = 1;            // TIO_DMA_PACKED
   int exact_plan = -1;           // TIO_EXACT_PLAN: -1 unset, else its value
   int exact_lean = -1;           // TIO_EXACT_LEAN: -1 unset (large exact float32 launches take resample_lean_exact_kernel), 0 never, 2 small launches too
   int nearest_exact = 1;         // TIO_NEAREST_EXACT=0: label maps without a fill rule keep the FAST-line kernel of rounds 3 - 5 (A/B)
-  int nearest_lds = -1;          // TIO_NEAREST_LDS: bytes of (unused) dynamic LDS per block of resample_nearest_exact_kernel — an occupancy knob (A/B; -1: the launch's own choice)
   int lean_pair = 1;             // TIO_LEAN_PAIR=0: one exact-coordinate launch per channel (until round 6; A/B)
   int lean_label = 1;            // TIO_LEAN_LABEL=0: a call's label channel never rides along the images' exact-coordinate launch (until round 6; A/B)
   int lean_multi = 1;            // TIO_LEAN_MULTI=0: no multi-pass bricks (boxes beyond the tile sample voxel by voxel, as until round 5: A/B)
@@ -45,9 +41,6 @@ struct EnvSwitches {
   int fast_fill_recheck = 1;     // TIO_FAST_FILL_RECHECK (0: the FAST fill rule decides alone, A/B)
   int conv_no_fuse = 0;          // TIO_CONV_NO_FUSE set
   int conv_ring = 0;             // TIO_CONV_RING set
-  int march_segs = 0;            // TIO_MARCH_SEGS (0 unset)
-  int march_order = -1;          // TIO_MARCH_ORDER (-1 unset)
-  int min_blocks = 0;            // TIO_MIN_BLOCKS (0 unset)
 };
 const EnvSwitches& env_switches();
 

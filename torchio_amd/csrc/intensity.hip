@@ -999,13 +999,11 @@ static int launch_conv(const void* x, void* y, float* tmp0, float* tmp1, int32_t
           const int64_t strips = lines;
           int want = static_cast<int>((8192 + strips - 1) / strips);
           want = std::max(1, std::min(want, std::max(1, n / 32)));
-          if (env_switches().march_segs > 0) want = env_switches().march_segs;  // experiments
           const int len = (n + want - 1) / want;
           grid.y = static_cast<unsigned>((n + len - 1) / len);
           grid.z = static_cast<unsigned>((static_cast<int64_t>(other) * bcs + kBlock / 64 - 1) / (kBlock / 64));
           lds = fused ? 4 * 272 * sizeof(float) : 0;
           a.tiles_a = 0;
-          if (env_switches().march_order >= 0) a.tiles_a = env_switches().march_order != 0;  // experiments
           if (a.tiles_a) std::swap(grid.x, grid.z);
 #define TIO_MARCH_VARIANT_F(RR, FM)                                                                                                  \
   {                                                                                                                                  \
@@ -1691,7 +1689,6 @@ extern "C" int tio_channel_min(const void* x, int32_t dtype, int32_t channels, i
   uint32_t* tickets = keys + ws_cap;
   const int64_t want = (n_spatial + kBlock - 1) / kBlock;
   int64_t cap = 512;  // two blocks per CU: measured 18 us per 64 MiB channel (2048 blocks: 34 us, the atomics and block tails add up)
-  if (env_switches().min_blocks > 0) cap = env_switches().min_blocks;  // experiments
   const unsigned gx = static_cast<unsigned>(want < cap ? want : cap);
 #define TIO_MIN(DT) \
   hipLaunchKernelGGL((min_reduce_kernel<DT>), dim3(gx, static_cast<unsigned>(channels)), dim3(kBlock), 0, s, x, n_spatial, keys, tickets, out_dev)

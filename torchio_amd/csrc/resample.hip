@@ -75,8 +75,6 @@ struct ResampleArgs {
   unsigned magic_k, magic_j, magic_i;  // multiply-high reciprocals of the tile counts (tile kernel)
   int cp_lds;    // floats of LDS reserved for the control points (0 = read them from global)
   int tile_cap;  // floats of LDS available for one staged input brick (tile kernel)
-  int ablate;    // profiling only (TIO_TILE_ABLATE): 1 = no staging, 2 = no sampling, 4 = trivial coordinates
-  int dma_packed;  // planned bricks: DMA instructions cover rows across x-plane boundaries (A/B: TIO_DMA_PACKED=0)
   int any_fill;      // an image of the launch has a fill rule
   int plan_multi;    // plan_bricks_kernel: bricks whose box exceeds the tile get pass boxes over halves / quarters of their planes (the exact-coordinate lean kernel reads them)
   int fill_recheck;  // FAST kernels: voxels whose in-bounds weight is within a margin of 1/2 take the exact chain's decision (A/B: TIO_FAST_FILL_RECHECK=0)
@@ -922,12 +920,12 @@ enum FloatRoadKind { kRoadGather, kRoadBrick, kRoadPlannedBrick, kRoadFastBrick,
 
 struct FloatRoad {
   FloatRoadKind kind = kRoadGather;
-  int variant = 0;          // brick roads: the brick shape (TIO_TILE_VARIANT; 0: 16 x 16 x 16)
   bool exact_lerp = false;  // lean exact: ATen's interpolation order (bit-identical to the brick kernel) instead of TIGHT's fused lerps
   int64_t bricks = 0;       // 16^3 bricks of the launch (planned roads: the plan's items)
   size_t lds = 0;           // dynamic LDS of the sampling kernel, bytes
   size_t plan_need = 0;     // bytes of the plan the road starts from (0: it does not)
-  int cp_lds = 0, tile_cap = 0, ablate = 0, fill_recheck = 0, dma_packed = 0, plan_multi = 0;  // what apply_road copies into ResampleArgs
+  int cp_lds = 0, tile_cap = 0, fill_recheck = 0, plan_multi = 0;  // what apply_road copies into ResampleArgs
+  int ablate = 0;  // TIO_TILE_ABLATE: the planned lean kernel's instrumented instantiation (the exact roads stay away from it)
   int interleave = 0, pair = 0;  // launch_lean: TIO_LEAN_INTERLEAVE, TIO_LEAN_PAIR (A/B)
 };
 FloatRoad choose_float_road(const tio_resample_geom& geom, const ResampleArgs& a, const FloatGroup& g, const EnvSwitches& env) {
@@ -942,27 +940,25 @@ FloatRoad choose_float_road(const tio_resample_geom& geom, const ResampleArgs& a
   if (static_cast<int64_t>(a.I) * a.J * a.K >= (1LL << 30)) use_tile = false;  // 32-bit byte offsets inside one input channel (f32 brick DMA)
   if (!use_tile) return r;
   r.kind = kRoadBrick;
-  r.variant = env.tile_variant;
   r.ablate = env.tile_ablate;
   r.fill_recheck = env.fast_fill_recheck;
   r.cp_lds = control_points_fit_lds(a) ? ((control_floats(a) + 3) & ~3) : 0;
   // default brick budget: whatever lets kTileBlocksPerCU blocks share the CU's 160 KiB (minus 2 KiB: LDS is allocated in granules, an exact third does not fit three times)
-  const int bpc = r.variant == 3 ? 2 : ((r.variant == 2 || r.variant == 4) ? 4 : kTileBlocksPerCU);  // resident blocks the variant is built for
-  const int cap = env.tile_lds_floats > 0 ? env.tile_lds_floats : kLdsFloatsPerCU / bpc - 512 - r.cp_lds - kTileRedInts;
+  const int cap = kLdsFloatsPerCU / kTileBlocksPerCU - 512 - r.cp_lds - kTileRedInts;
   const int max_cap = kLdsFloatsPerCU - r.cp_lds - kTileRedInts;
   r.tile_cap = cap < kTileMinCap ? kTileMinCap : (cap > max_cap ? max_cap : cap);
   r.lds = static_cast<size_t>(r.cp_lds + kTileRedInts + r.tile_cap) * sizeof(float);
   r.bricks = static_cast<int64_t>(a.B) * ((a.Io + 15) / 16) * ((a.Jo + 15) / 16) * ((a.Ko + 15) / 16);
   const size_t plan_plain = static_cast<size_t>(a.B) * 16 + static_cast<size_t>(r.bricks) * kDescInts;  // (ints behind the header)
   // fast intensity path: float32 trilinear images only (nearest / label images need the exact coordinates)
-  const bool fast = geom.precision == TIO_PRECISION_FAST && g.dtmode == 0 && !a.any_nearest && r.variant == 0 && !env.resample_exact;
+  const bool fast = geom.precision == TIO_PRECISION_FAST && g.dtmode == 0 && !a.any_nearest && !env.resample_exact;
   // The lean planned kernel with the reference's own coordinates (resample_lean_exact.hpp).  TIO_PRECISION_TIGHT: fused interpolation on exact coordinates / taps / fill
   // decisions; TIO_PRECISION_EXACT: ATen's interpolation order too, bit-identical to the brick kernel (TIO_EXACT_LEAN=0 keeps large exact launches on the brick kernel, =2
   // sends small ones to the lean kernel as well: A/B and tests).  Float32 trilinear images only, divisors the short division is proven for, unit spacing whenever a
   // displacement is divided by it; everything else runs the exact brick kernel.
   const bool tight = geom.precision == TIO_PRECISION_TIGHT && !env.resample_exact;  // (TIO_RESAMPLE_EXACT: the A/B switch forces ATen's interpolation order too)
   const bool lean_exact = !fast && (tight || ((geom.precision == TIO_PRECISION_EXACT || geom.precision == TIO_PRECISION_TIGHT) && env.exact_lean != 0)) &&
-                          g.dtmode == 0 && !a.any_nearest && r.variant == 0 && r.ablate == 0 && a.short_div != 0 && (a.cp == nullptr || a.unit_spacing != 0);
+                          g.dtmode == 0 && !a.any_nearest && r.ablate == 0 && a.short_div != 0 && (a.cp == nullptr || a.unit_spacing != 0);
   if (fast || lean_exact) {
     // Planned bricks (resample_fast.hpp): a planning kernel, then one block per brick that starts from its 64-byte descriptor. Needs 16-byte rows for the LDS-DMA and
     // control cells at least a brick wide (the box comes from <= 27 vertices); small launches keep the single-kernel road (the planning kernel and the gap before the
@@ -982,11 +978,10 @@ FloatRoad choose_float_road(const tio_resample_geom& geom, const ResampleArgs& a
       r.exact_lerp = !tight;
       // the largest tile three blocks of which fit a CU: LDS is handed out in granules of 1 280 bytes here (measured: 13 440 floats keep three blocks resident, 13 568 drop
       // to two — profiles/r04_tile_cap.log)
-      const int cap_p = env.tile_lds_floats > 0 ? env.tile_lds_floats : (kLdsFloatsPerCU / kTileBlocksPerCU) / 320 * 320;
+      const int cap_p = (kLdsFloatsPerCU / kTileBlocksPerCU) / 320 * 320;
       r.tile_cap = cap_p < kTileMinCap ? kTileMinCap : (cap_p > kLdsFloatsPerCU ? kLdsFloatsPerCU : cap_p);
       r.cp_lds = 0;
       r.lds = static_cast<size_t>(r.tile_cap) * sizeof(float);
-      r.dma_packed = env.dma_packed;  // DMA instructions that cover rows across x-plane boundaries (TIO_DMA_PACKED=0: A/B)
       r.interleave = env.lean_interleave;
       r.pair = env.lean_pair;
       // the exact-coordinate kernel stages bricks whose box exceeds the tile in passes over their planes (pass boxes behind the descriptors) — on the hint of a caller who
@@ -1010,7 +1005,7 @@ FloatRoad choose_float_road(const tio_resample_geom& geom, const ResampleArgs& a
   // Large affine-only exact launches of 16^3 bricks are planned too (resample_tile.hpp: the planned box only decides what is staged); TIO_EXACT_PLAN=0 switches it off, =2
   // forces it for small launches (A/B, tests).  Measured (8 x 256^3): affine 0.497 -> 0.478 ms; elastic launches LOSE (0.588 -> 0.610: 27 vertices with their control-point
   // reads per brick cost the planner more than the brick kernel's own reduction), and so do small ones.
-  if (r.variant == 0 && r.ablate == 0 && a.cp == nullptr && env.exact_plan != 0 && (r.bricks >= kPlannedMinBricks || env.exact_plan == 2) && r.bricks < (1LL << 26)) {
+  if (r.ablate == 0 && a.cp == nullptr && env.exact_plan != 0 && (r.bricks >= kPlannedMinBricks || env.exact_plan == 2) && r.bricks < (1LL << 26)) {
     r.kind = kRoadPlannedBrick;
     // (every plan starts behind kPlanHeaderInts ints: the list header of the lean exact road, which shares the stream's leased workspace and must find it zero)
     r.plan_need = (kPlanHeaderInts + plan_plain) * sizeof(int);
@@ -1019,8 +1014,8 @@ FloatRoad choose_float_road(const tio_resample_geom& geom, const ResampleArgs& a
 }
 
 void apply_road(ResampleArgs& a, const FloatRoad& r) {
-  a.fill_recheck = r.fill_recheck; a.ablate = r.ablate; a.cp_lds = r.cp_lds; a.tile_cap = r.tile_cap;
-  a.dma_packed = r.dma_packed; a.plan_multi = r.plan_multi;
+  a.fill_recheck = r.fill_recheck; a.cp_lds = r.cp_lds; a.tile_cap = r.tile_cap;
+  a.plan_multi = r.plan_multi;
   for (int i = 0; i < a.n_images && r.kind != kRoadGather; i++) a.any_fill |= a.img[i].fill != nullptr ? 1 : 0;
 }
 
@@ -1035,7 +1030,7 @@ LeanArgs make_lean_args(const ResampleArgs& a, const FloatRoad& r, const int* pl
   la.sci = a.scale_i; la.scj = a.scale_j; la.sck = a.scale_k;
   for (int e = 0; e < 3; e++) la.dsc[e] = a.rsp[e] * (a.affine_first ? a.half_h[e] / a.dh[e] : 1.0f);
   la.hx = a.size_m1[0]; la.hy = a.size_m1[1]; la.hz = a.size_m1[2];
-  la.affine_first = a.affine_first; la.ablate = a.ablate;
+  la.affine_first = a.affine_first; la.ablate = r.ablate;
   la.mapping = a.mapping; la.mapping_batched = a.mapping_batched; la.unit_spacing = a.unit_spacing; la.fill_recheck = a.fill_recheck;
   for (int e = 0; e < 3; e++) { la.sp[e] = a.sp[e]; la.rsp[e] = a.rsp[e]; la.den[e] = a.den[e]; la.rden[e] = a.rden[e]; }
   for (int e = 0; e < 3; e++) { la.dh[e] = a.dh[e]; la.rdh[e] = a.rdh[e]; la.half_h[e] = a.half_h[e]; }
@@ -1068,8 +1063,8 @@ int launch_nearest(NearestArgs& nn, bool short_div, bool floats_alone, const Env
   const bool exact = env.nearest_exact != 0 && nn.any_fill == 0 && rows && short_div && (nn.cp == nullptr || nn.unit_spacing != 0);
   // resident blocks per CU through UNUSED dynamic LDS: without control points the kernel holds 61 registers (eight blocks per CU), and eight blocks' slanted input
   // footprints evict one another's cache lines — three blocks per CU measured 0.236 -> 0.210 ms (int16) and 0.344 -> 0.286 (int32) on 8 x 256^3 at the bench's ranges, uint8
-  // 0.172 -> 0.177; with control points (95 registers, five blocks) the launch is arithmetic bound and loses from four blocks down (profiles/r06_labels.md).  TIO_NEAREST_LDS: A/B
-  const unsigned exact_lds = env.nearest_lds >= 0 ? static_cast<unsigned>(env.nearest_lds) : (nn.cp == nullptr ? 52000u : 0u);
+  // 0.172 -> 0.177; with control points (95 registers, five blocks) the launch is arithmetic bound and loses from four blocks down (profiles/r06_labels.md)
+  const unsigned exact_lds = nn.cp == nullptr ? 52000u : 0u;
   for (int es = 1; es <= 8; es *= 2) {
     bool present = false;
     for (int i = 0; i < nn.n_images; i++) present = present || nn.img[i].es == es;
@@ -1117,49 +1112,37 @@ int launch_gather(ResampleArgs& a, int dtmode, hipStream_t s) {
   return status != TIO_OK ? status : check_launch("tio_resample3d");
 }
 
-// one block per brick of TI x TJ x TK voxels; only 16^3 bricks can start from a plan (nullptr: in-kernel boxes)
-int launch_brick_kernel(BrickKernel kernel, int ti, int tj, int tk, ResampleArgs& a, size_t lds, const int* plan, hipStream_t s) {
+// one block of 256 threads per 16 x 16 x 16 brick, from a plan or (nullptr) with in-kernel boxes
+int launch_brick_kernel(BrickKernel kernel, ResampleArgs& a, size_t lds, const int* plan, hipStream_t s) {
   unsigned blocks = 0;
-  if (const int st = set_tiles(a, ti, tj, tk, &blocks)) return st;
+  if (const int st = set_tiles(a, 16, 16, 16, &blocks)) return st;
   if (const int st = reserve_lds(kernel, lds)) return st;
-  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(tj * tk), lds, s, a, (ti == 16 && tj == 16 && tk == 16) ? plan : static_cast<const int*>(nullptr));
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), lds, s, a, plan);
   return check_launch("tio_resample3d");
 }
 
-// F32_ONLY: an experimental shape (TIO_TILE_VARIANT), built for float32 launches only — others take the default shape
-template <int TI, int TJ, int TK, int OCC, bool F32_ONLY>
-int launch_brick_shape(ResampleArgs& a, int dtmode, size_t lds, const int* plan, hipStream_t s) {
-  if constexpr (F32_ONLY) {
-    if (dtmode != 0) return launch_brick_shape<16, 16, 16, 3, false>(a, dtmode, lds, plan, s);
-  }
+// the brick kernel (three blocks per CU) in the instantiation of the launch's element types
+int launch_brick_dtmode(ResampleArgs& a, int dtmode, size_t lds, const int* plan, hipStream_t s) {
   const BrickKernel kernel = with_bools([&](auto elastic) -> BrickKernel {
-    if constexpr (!F32_ONLY) {
-      if (dtmode == 1) return resample_tile_kernel<elastic.value, 1, TI, TJ, TK, OCC>;
-      if (dtmode != 0) return resample_tile_kernel<elastic.value, 2, TI, TJ, TK, OCC>;
-    }
-    return resample_tile_kernel<elastic.value, 0, TI, TJ, TK, OCC>;
+    if (dtmode == 1) return resample_tile_kernel<elastic.value, 1, 16, 16, 16, 3>;
+    if (dtmode != 0) return resample_tile_kernel<elastic.value, 2, 16, 16, 16, 3>;
+    return resample_tile_kernel<elastic.value, 0, 16, 16, 16, 3>;
   }, a.cp != nullptr);
-  return launch_brick_kernel(kernel, TI, TJ, TK, a, lds, plan, s);
+  return launch_brick_kernel(kernel, a, lds, plan, s);
 }
 
 // brick, planned brick and FAST brick: resample_tile_kernel
 int launch_brick(const tio_resample_geom* geom, ResampleArgs& a, const FloatRoad& r, int dtmode, hipStream_t s) {
   if (r.kind == kRoadFastBrick) {
     const BrickKernel kernel = with_bools([](auto elastic) -> BrickKernel { return resample_tile_kernel<elastic.value, 0, 16, 16, 16, 3, true>; }, a.cp != nullptr);
-    return launch_brick_kernel(kernel, 16, 16, 16, a, r.lds, nullptr, s);
+    return launch_brick_kernel(kernel, a, r.lds, nullptr, s);
   }
   Plan plan;  // (a lease is held until the brick kernel is enqueued)
   if (r.kind == kRoadPlannedBrick) {
     int n_items = 0;
     if (const int st = plan_bricks(geom, a, r.plan_need, s, &plan, &n_items)) return st;
   }
-  switch (r.variant) {
-    case 1: return launch_brick_shape<16, 8, 32, 3, true>(a, dtmode, r.lds, plan.ptr, s);
-    case 2: return launch_brick_shape<8, 8, 32, 4, true>(a, dtmode, r.lds, plan.ptr, s);
-    case 3: return launch_brick_shape<8, 16, 32, 2, true>(a, dtmode, r.lds, plan.ptr, s);  // 512 threads, 2 blocks per CU
-    case 4: return launch_brick_shape<8, 16, 16, 4, true>(a, dtmode, r.lds, plan.ptr, s);
-    default: return launch_brick_shape<16, 16, 16, 3, false>(a, dtmode, r.lds, plan.ptr, s);
-  }
+  return launch_brick_dtmode(a, dtmode, r.lds, plan.ptr, s);
 }
 
 // planned FAST (TIO_PLANNED_LEAN=0): one launch of resample_planned_kernel for all images and channels
@@ -1208,7 +1191,7 @@ int launch_lean(const tio_resample_geom* geom, ResampleArgs& a, const FloatRoad&
     kernel = with_bools([](auto e, auto x, auto f) -> LeanKernel { return resample_lean_exact_all_kernel<e.value, x.value, f.value>; }, elastic, r.exact_lerp, fold);
   else if (lean_exact)
     kernel = with_bools([](auto e, auto x, auto f) -> LeanKernel { return resample_lean_exact_kernel<e.value, x.value, 3, f.value>; }, elastic, r.exact_lerp, fold);
-  else if (a.ablate != 0)  // TIO_TILE_ABLATE: the instrumented instantiation (experiments only)
+  else if (r.ablate != 0)  // TIO_TILE_ABLATE: the instrumented instantiation (experiments only)
     kernel = with_bools([](auto e) -> LeanKernel { return resample_planned_lean_kernel<e.value, 16, 16, 16, 3, true>; }, elastic);
   else  // (the folded minimum: the instantiation whose element-0 bricks track what they store)
     kernel = with_bools([](auto e, auto f) -> LeanKernel { return resample_planned_lean_kernel<e.value, 16, 16, 16, 3, false, f.value>; }, elastic, fold);

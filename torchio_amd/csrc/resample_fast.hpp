@@ -345,67 +345,15 @@ __device__ __forceinline__ void stage_lanes(StageLanes& sl, int cpr, int K, int 
   sl.goff = static_cast<unsigned>(sl.row_l * K + 4 * ch_l) * 4u;
 }
 
-// This wave's share (x-planes wave, wave + NW, ...) of the LDS-DMA of one box (dense layout: row
-// pitch = 4 cpr floats).  Interior boxes: nothing but scalar pointer increments between two DMA
-// instructions; boxes that stick out of the volume check rows per lane and store zeros for the
-// chunks outside.
-template <int NW>
-__device__ __forceinline__ int stream_stage(float* __restrict__ tile, const float* __restrict__ src, const StreamBox& bx, int I, int J,
-                                             int K, int wave, int lane, StageLanes& sl) {
-  typedef __attribute__((address_space(1))) const char* global_byte_ptr;
-  stage_lanes(sl, bx.cpr, K, lane);
-  const int rpi = sl.rpi;
-  // full groups of rpi rows, then one partial group (uniform float division: tiny operands, exact after the nudge)
-  const int full = __builtin_amdgcn_readfirstlane(static_cast<int>((static_cast<float>(bx.Ly) + 0.5f) * __builtin_amdgcn_rcpf(static_cast<float>(rpi))));
-  const int rest = bx.Ly - full * rpi;
-  const int64_t plane_b = static_cast<int64_t>(J) * K * 4;         // bytes between x-planes of the volume
-  const int64_t group_b = static_cast<int64_t>(rpi) * K * 4;       // bytes between row groups
-  const int dplane = bx.Ly * bx.cpr * 4, dgroup = rpi * bx.cpr * 4;  // the same steps in LDS floats
-  global_byte_ptr gp = (global_byte_ptr)(src) + ((static_cast<int64_t>(bx.bx0 + wave) * J + bx.by0) * K + bx.za) * 4;
-  float* lp = tile + wave * dplane;
-  int issued = 0;  // DMA instructions of this wave (scalar)
-  if (bx.interior) {
-    const bool tail_ok = sl.lane_ok & (sl.row_l < rest);
-    for (int xr = wave; xr < bx.Lx; xr += NW) {
-      issued += full + (rest > 0 ? 1 : 0);
-      global_byte_ptr g = gp;
-      float* l = lp;
-      for (int q = 0; q < full; q++) {
-        if (sl.lane_ok) __builtin_amdgcn_global_load_lds(g + sl.goff, (fast_lds_wptr)(l), 16, 0, 0);
-        g += group_b; l += dgroup;
-      }
-      if (rest > 0 && tail_ok) __builtin_amdgcn_global_load_lds(g + sl.goff, (fast_lds_wptr)(l), 16, 0, 0);
-      gp += NW * plane_b; lp += NW * dplane;
-    }
-    return issued;
-  }
-  const bool ch_ok = static_cast<unsigned>(bx.za + sl.gz_rel) < static_cast<unsigned>(K);
-  const int groups = full + (rest > 0 ? 1 : 0);
-  for (int xr = wave; xr < bx.Lx; xr += NW) {
-    const bool plane_ok = static_cast<unsigned>(bx.bx0 + xr) < static_cast<unsigned>(I);
-    global_byte_ptr g = gp;
-    float* l = lp;
-    for (int q = 0; q < groups; q++) {
-      const int r0 = q * rpi;
-      const bool in_box = sl.lane_ok & (sl.row_l < bx.Ly - r0);
-      const bool in_vol = in_box & plane_ok & ch_ok & (static_cast<unsigned>(bx.by0 + r0 + sl.row_l) < static_cast<unsigned>(J));
-      if (__builtin_amdgcn_ballot_w64(in_vol) != 0ull) issued++;
-      if (in_vol) __builtin_amdgcn_global_load_lds(g + sl.goff, (fast_lds_wptr)(l), 16, 0, 0);
-      else if (in_box) lds_zero_chunk(l + 4 * lane);
-      g += group_b; l += dgroup;
-    }
-    gp += NW * plane_b; lp += NW * dplane;
-  }
-  return issued;
-}
-
-// The same box with the DMA instructions PACKED (round 3): the rows of the box are one dense sequence in LDS (x-plane
-// after x-plane), and a wave instruction simply covers the next rpi rows of that sequence, whatever x-plane they belong
-// to.  stream_stage issues ceil(Ly / rpi) instructions per x-plane — for the bench geometry (Ly ~ 21, rpi = 10) three,
-// the third carrying a single row — i.e. 63 instructions for a box of 44 KiB; packed, the same box takes 45.  A
+// This wave's share (instructions wave, wave + NW, ...) of the LDS-DMA of one box, PACKED (round 3): the rows of the
+// box are one dense sequence in LDS (x-plane after x-plane, row pitch = 4 cpr floats), and a wave instruction simply
+// covers the next rpi rows of that sequence, whatever x-plane they belong to.  One instruction sequence per x-plane
+// would take ceil(Ly / rpi) instructions for each — for the bench geometry (Ly ~ 21, rpi = 10) three, the third
+// carrying a single row — i.e. 63 instructions for a box of 44 KiB; packed, the same box takes 45.  A
 // vector-memory instruction costs this kernel's CU about the same whatever it moves (profiles/r03_resample.md), so the
 // count is what matters.  The price is a per-lane address (row -> x-plane and row inside it, advanced incrementally)
-// instead of scalar pointer increments: a handful of vector instructions per DMA instruction.
+// instead of scalar pointer increments: a handful of vector instructions per DMA instruction.  Boxes that stick out
+// of the volume check rows per lane and store zeros for the chunks outside.
 template <int NW, int AUX = 0>
 __device__ __forceinline__ int stream_stage_packed(float* __restrict__ tile, const float* __restrict__ src, const StreamBox& bx, int I, int J,
                                                     int K, int wave, int lane, StageLanes& sl, int skip_mod = 0) {
@@ -844,8 +792,7 @@ __global__ __launch_bounds__(TJ* TK, (TJ * TK) / 256 * OCC) void resample_planne
       const bool has_fill = g.fill != nullptr;
       const float fillv = has_fill ? ((const_float_ptr)g.fill)[c] : 0.0f;
       if (!first) __syncthreads();  // the previous channel's taps are read
-      if (a.dma_packed) stream_stage_packed<NW>(s_tile, in_chan, bx, a.I, a.J, a.K, wave, lane, sl);
-      else stream_stage<NW>(s_tile, in_chan, bx, a.I, a.J, a.K, wave, lane, sl);
+      stream_stage_packed<NW>(s_tile, in_chan, bx, a.I, a.J, a.K, wave, lane, sl);
       if (first) {
 #pragma unroll
         for (int r = 0; r < 3; r++) col3[r] = __builtin_fmaf(f.m[4 * r + 1], fv, f.m[4 * r + 2] * fw);

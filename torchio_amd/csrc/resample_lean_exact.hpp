@@ -508,10 +508,7 @@ __device__ __forceinline__ void lean_exact_label_issue(const float (&X)[16], con
     __builtin_amdgcn_sched_barrier(0);
   }
   // (exactly sixteen vector-memory instructions whatever the element size: the wait above counts them)
-  if (ka->ablate & 256) {  // (measurement: TIO_TILE_ABLATE=256 — no label loads; sixteen loads of offset 0 keep the count)
-#pragma unroll
-    for (int t = 0; t < 16; t++) vlab[t] = __builtin_amdgcn_raw_buffer_load_b8(rsrc, 0u, 0, 0) + boffs[t];
-  } else if (es == 1) {
+  if (es == 1) {
 #pragma unroll
     for (int t = 0; t < 16; t++) vlab[t] = __builtin_amdgcn_raw_buffer_load_b8(rsrc, boffs[t], 0, 0);
   } else if (es == 2) {
@@ -555,7 +552,6 @@ __device__ __forceinline__ void lean_exact_label_store(const unsigned (&vlab)[16
       }                                                                                         \
     }                                                                                           \
   }
-  if (ka->ablate & 512) return;  // (measurement: TIO_TILE_ABLATE=512 — no label stores)
   if (es == 1) TIO_LE_LABEL_STORES(uint8_t)
   else if (es == 2) TIO_LE_LABEL_STORES(uint16_t)
   else TIO_LE_LABEL_STORES(uint32_t)

@@ -314,66 +314,6 @@ __device__ __forceinline__ TileBox load_box(const int* s) {
 }
 
 // ---- stage the box in LDS: dense rows of Lz floats, positions outside the volume are 0 --
-// float32, K % 4 == 0, 16-byte aligned base: one 16-byte chunk per lane, LPR lanes per
-// row (a power of two ≥ Lz/4), row coordinates advanced incrementally (no divisions in
-// the loop).
-template <int NT>
-__device__ __forceinline__ void stage_brick_f32x4(float* __restrict__ tile, const float* __restrict__ src, int tid,
-                                                  const TileBox& bx, int I, int J, int K) {
-  const int cpr = bx.Lz >> 2;  // 16-byte chunks per row
-  if (cpr > 64) {              // absurdly long rows: plain strided loop
-    const unsigned total = static_cast<unsigned>(bx.Lx * bx.Ly) * cpr;
-    const unsigned m_cpr = fastdiv_magic(cpr), m_ly = fastdiv_magic(bx.Ly);
-    for (unsigned id = tid; id < total; id += NT) {
-      const unsigned row = fastdiv(id, m_cpr, cpr), ch = id - row * cpr;
-      const unsigned xr = fastdiv(row, m_ly, bx.Ly), yr = row - xr * bx.Ly;
-      const int gx = bx.bx0 + static_cast<int>(xr), gy = bx.by0 + static_cast<int>(yr), gz = bx.za + 4 * static_cast<int>(ch);
-      float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      if ((static_cast<unsigned>(gx) < static_cast<unsigned>(I)) & (static_cast<unsigned>(gy) < static_cast<unsigned>(J)) &
-          (static_cast<unsigned>(gz) < static_cast<unsigned>(K)))
-        v = *reinterpret_cast<const float4*>(src + (gx * J + gy) * K + gz);
-      *reinterpret_cast<float4*>(tile + 4 * id) = v;
-    }
-    return;
-  }
-  const int lpr_log = cpr <= 4 ? 2 : (cpr <= 8 ? 3 : (cpr <= 16 ? 4 : (cpr <= 32 ? 5 : 6)));
-  const int rows = bx.Lx * bx.Ly;
-  const int rpi = NT >> lpr_log;  // rows per block iteration
-  const int ch = tid & ((1 << lpr_log) - 1);
-  int r = tid >> lpr_log;
-  const int gz = bx.za + 4 * ch;
-  const bool ch_ok = (ch < cpr) & (static_cast<unsigned>(gz) < static_cast<unsigned>(K));
-  const unsigned m_ly = fastdiv_magic(bx.Ly);
-  int xr = static_cast<int>(fastdiv(r, m_ly, bx.Ly));
-  int yr = r - xr * bx.Ly;
-  const int dx = static_cast<int>(fastdiv(rpi, m_ly, bx.Ly)), dy = rpi - dx * bx.Ly;  // uniform row step
-  int lds = r * bx.Lz + 4 * ch;
-  const int lds_step = rpi * bx.Lz;
-  // All of a thread's chunks are requested before the first one is written to LDS: one
-  // memory round trip per brick instead of one per group (U * rpi rows cover the box in a
-  // single sweep for every box that fits the default LDS budget).
-  constexpr int U = 10;
-  while (r < rows) {  // NB: r differs between lanes by < rpi, the loop is exec-masked at the tail
-    float4 v[U];
-    const int r0 = r, lds0 = lds;
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      const int gx = bx.bx0 + xr, gy = bx.by0 + yr;
-      v[u] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      if ((r < rows) & ch_ok & (static_cast<unsigned>(gx) < static_cast<unsigned>(I)) & (static_cast<unsigned>(gy) < static_cast<unsigned>(J)))
-        v[u] = *reinterpret_cast<const float4*>(src + (gx * J + gy) * K + gz);
-      r += rpi; lds += lds_step;
-      xr += dx; yr += dy;
-      if (yr >= bx.Ly) { yr -= bx.Ly; xr += 1; }
-    }
-    if (ch < cpr) {
-#pragma unroll
-      for (int u = 0; u < U; u++)
-        if (r0 + u * rpi < rows) *reinterpret_cast<float4*>(tile + lds0 + u * lds_step) = v[u];
-    }
-  }
-}
-
 // Sixteen zero bytes for a chunk of the box that lies outside the volume — as an instruction the compiler does not see (round 5,
 // first found in resample_lean_exact.hpp; used by every staging loop that mixes DMA and zero chunks): in front of a plain LDS
 // store it puts `s_waitcnt vmcnt(0)`, because the store may alias an LDS-DMA in flight for all it knows, and every DMA
@@ -602,7 +542,6 @@ __device__ __forceinline__ void tile_channel(const ResampleArgs& a, const ImgArg
                                              bool prestaged = false) {
   constexpr int NQ = 4, QT = TI / NQ;
   const float hx = a.size_m1[0], hy = a.size_m1[1], hz = a.size_m1[2];
-  const int t_begin = q_begin * QT, t_end = min(q_end * QT, i_count);
   const bool vec_ok = (g.dtype == TIO_F32) & ((a.K & 3) == 0) & ((reinterpret_cast<uintptr_t>(g.in) & 15) == 0);
   TileAddr ta;
   ta.ox = static_cast<float>(bx.bx0); ta.oy = static_cast<float>(bx.by0); ta.oz = static_cast<float>(bx.za);
@@ -612,14 +551,11 @@ __device__ __forceinline__ void tile_channel(const ResampleArgs& a, const ImgArg
   const int es = dtype_size(g.dtype);
   const int64_t bc = static_cast<int64_t>(b) * g.channels + c;
   if (!prestaged) __syncthreads();  // previous brick of this block fully consumed
-  if (a.ablate & 1) {
-  } else if (prestaged) {  // the caller issued the DMA before phase A
-    tile_dma_wait();
-  } else if (vec_ok && !(a.ablate & 8)) {
-    stage_brick_dma<NT>(s_tile, static_cast<const float*>(g.in) + bc * n_in, tid, bx, a.I, a.J, a.K);
+  if (prestaged) {  // the caller issued the DMA before phase A
     tile_dma_wait();
   } else if (vec_ok) {
-    stage_brick_f32x4<NT>(s_tile, static_cast<const float*>(g.in) + bc * n_in, tid, bx, a.I, a.J, a.K);
+    stage_brick_dma<NT>(s_tile, static_cast<const float*>(g.in) + bc * n_in, tid, bx, a.I, a.J, a.K);
+    tile_dma_wait();
   } else {
     stage_brick_generic<NT, DTMODE>(s_tile, static_cast<const char*>(g.in) + bc * n_in * es, g.dtype, tid, bx, a.I, a.J, a.K);
   }
@@ -637,12 +573,6 @@ __device__ __forceinline__ void tile_channel(const ResampleArgs& a, const ImgArg
   const int64_t slab_b = static_cast<int64_t>(slab) * es;
   char* out_c = static_cast<char*>(g.out) + (bc * n_out + static_cast<int64_t>(i_begin) * slab) * es;
   const unsigned urow = static_cast<unsigned>(row) * static_cast<unsigned>(es);
-  if (a.ablate & 2) {
-#pragma unroll
-    for (int t = 0; t < TI; t++)
-      if (col_active && t >= t_begin && t < t_end) store_at<DTMODE>(out_c + t * slab_b, g.dtype, urow, X[t] + Y[t] + Z[t]);
-    return;
-  }
   // `full` (block uniform): every thread owns a real column and all TI planes exist, so the
   // hot loops carry no predication and a quarter's LDS reads are all in flight before its
   // first accumulation.
@@ -932,7 +862,7 @@ __global__ __launch_bounds__(TJ* TK, (TJ * TK) / 256 * OCC) void resample_tile_k
   if (have_box) {
     const ImgArgs& g0 = a.img[0];
     prestaged = (a.n_images == 1) & (g0.channels == 1) & (g0.interp == TIO_LINEAR) & (box_full.fits != 0) & (box_full.outside == 0) &
-                (g0.dtype == TIO_F32) & ((a.K & 3) == 0) & ((reinterpret_cast<uintptr_t>(g0.in) & 15) == 0) & (a.ablate == 0);
+                (g0.dtype == TIO_F32) & ((a.K & 3) == 0) & ((reinterpret_cast<uintptr_t>(g0.in) & 15) == 0);
     if (prestaged)
       stage_brick_dma<NT>(s_tile, static_cast<const float*>(g0.in) + static_cast<int64_t>(b) * n_in, tid, box_full, a.I, a.J, a.K);
   }
