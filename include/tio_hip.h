@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define TIO_ABI_VERSION 17
+#define TIO_ABI_VERSION 18
 #define TIO_MAX_IMAGES 8 /* images resampled per launch with shared coordinates */
 
 typedef enum tio_status {
@@ -288,6 +288,49 @@ int tio_separable_conv3d(const void* x, void* y, void* tmp, int32_t dtype,
                          const float* taps_dev, int32_t taps_batched,
                          int32_t tap_stride, const int32_t radius[3],
                          const uint8_t* skip_dev, void* stream);
+
+/*
+ * What tio_separable_conv3d / tio_blur_fused would launch for these arguments (ABI 18).  Host-only: nothing is
+ * enqueued and no pointer is read — the launcher and this function share one decision function, so the answer is
+ * the launch.  One tio_conv_pass per kernel launch, in launch order.
+ *   aligned16: non-zero = x, y and tmp are 16-byte aligned; 0 = x is not (no 16-byte kernel runs);
+ *   has_skip:  a skip_dev would be passed;
+ *   bias_on / noise_on (0, 1, 2) / fast_math: the stages of tio_blur_fused; any of them non-zero asks about
+ *              tio_blur_fused (TIO_ERR_UNSUPPORTED_CONFIG where that entry point returns it).
+ * Returns the number of passes (0 .. 3; 0 = every radius is 0, or an empty batch) or a negative tio_status:
+ * TIO_ERR_INVALID_ARGUMENT where the launch would be refused before anything runs — a pass whose lines, counted as
+ * (the other non-K axis, or I for the K pass) x batch x channels, exceed 65 535.
+ * Honours TIO_CONV_RING and TIO_CONV_NO_FUSE as the launcher does.
+ */
+typedef enum tio_conv_family {
+  TIO_CONV_LINE = 0,  /* generic I / J kernel: any dtype, any alignment; 32-row tiles */
+  TIO_CONV_K = 1,     /* generic K kernel */
+  TIO_CONV_K_V4 = 2,  /* 16-byte K kernel */
+  TIO_CONV_MARCH = 3, /* register-window marching kernel (I / J, radius <= 8) */
+  TIO_CONV_RING = 4   /* LDS-ring marching kernel (I / J, radius <= 16) */
+} tio_conv_family;
+
+typedef struct tio_conv_pass {
+  int32_t axis;             /* 0 = I, 1 = J, 2 = K */
+  int32_t family;           /* tio_conv_family */
+  int32_t radius;           /* run-time radius along `axis` */
+  int32_t radius_class;     /* TIO_CONV_MARCH: the compile-time radius of the instantiation; otherwise 0 */
+  int32_t radius_k;         /* > 0: the K taps of this radius are applied to every row the pass stores (fused J + K) */
+  int32_t pre_bias;         /* the bias field multiplies the rows this pass loads */
+  int32_t post_noise;       /* 0 = none, 1 = Philox draws, 2 = explicit draws added to the rows this pass stores */
+  int32_t fma;              /* taps accumulate with fused multiply-adds */
+  int32_t grid[3];
+  int32_t segments;         /* I / J passes: pieces a line is cut into along the axis (0 for K passes) */
+  int32_t rows_per_segment; /* I / J passes: output rows of every piece but the last, which holds the rest */
+  int32_t k_tiles;          /* blocks along K */
+  int32_t lds_bytes;        /* dynamic LDS of the launch */
+  int32_t last;             /* the pass stores into y (in the dtype of the call) */
+} tio_conv_pass;
+
+int tio_separable_conv3d_passes(int32_t dtype, int32_t batch, int32_t channels, const int32_t shape[3],
+                                const int32_t radius[3], int32_t aligned16, int32_t has_skip,
+                                int32_t bias_on, int32_t noise_on, int32_t fast_math,
+                                tio_conv_pass out_passes[3]);
 
 /*
  * Backward of tio_separable_conv3d with respect to x (ABI 16): gx = A_I^T A_J^T A_K^T gy, where A_a is the

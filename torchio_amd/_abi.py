@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 MAX_IMAGES = 8
 
 # tio_status
@@ -80,6 +80,31 @@ class PatchPlacement(C.Structure):
     """``tio_patch_placement`` (host memory)."""
 
     _fields_ = [("dst_ini", C.c_int32 * 3), ("src_ini", C.c_int32 * 3), ("extent", C.c_int32 * 3)]
+
+
+# tio_conv_family
+CONV_LINE, CONV_K, CONV_K_V4, CONV_MARCH, CONV_RING = 0, 1, 2, 3, 4
+
+
+class ConvPass(C.Structure):
+    """``tio_conv_pass``: one launch of the separable stencil as ``tio_separable_conv3d_passes`` reports it."""
+
+    _fields_ = [
+        ("axis", C.c_int32),
+        ("family", C.c_int32),
+        ("radius", C.c_int32),
+        ("radius_class", C.c_int32),
+        ("radius_k", C.c_int32),
+        ("pre_bias", C.c_int32),
+        ("post_noise", C.c_int32),
+        ("fma", C.c_int32),
+        ("grid", C.c_int32 * 3),
+        ("segments", C.c_int32),
+        ("rows_per_segment", C.c_int32),
+        ("k_tiles", C.c_int32),
+        ("lds_bytes", C.c_int32),
+        ("last", C.c_int32),
+    ]
 
 
 MAX_PATCHES = 32
@@ -169,6 +194,11 @@ HIP_ONLY_PROTOTYPES = {
     "mt19937_device_snapshots": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "mt19937_add_noise_device": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    # the stencil dispatcher's choice for one call (ABI 18): host-only, nothing is enqueued
+    "separable_conv3d_passes": (
+        C.c_int,
+        [C.c_int32, C.c_int32, C.c_int32, _I32x3, _I32x3, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(ConvPass)],
     ),
     "blur_fused": (
         C.c_int,

@@ -910,64 +910,72 @@ struct ConvFuse {  // optional pointwise stages of tio_blur_fused
   bool any() const { return bias_coarse != nullptr || noise_on != 0; }
 };
 
-template <int DT>
-static int launch_conv(const void* x, void* y, float* tmp0, float* tmp1, int32_t batch, int32_t channels,
-                       const int32_t shape[3], const float* taps, int taps_batched, int tap_stride,
-                       const int32_t radius[3], const uint8_t* skip, hipStream_t stream, const ConvFuse& fuse = ConvFuse()) {
+// ---- the dispatcher's decisions (host only) --------------------------------------------------
+// plan_conv decides everything launch_conv launches — the pass list and, per pass, the kernel family, the compile-time
+// radius of the marching kernel, the stages that ride along, the grid and the dynamic LDS — from counts and alignment bits
+// alone: it reads no pointer and enqueues nothing.  launch_conv and tio_separable_conv3d_passes both go through it, so what
+// the latter reports is what the former launches (tests/test_stencil_passes.py pins the thresholds on the CPU).
+constexpr unsigned kAlignedX = 1u, kAlignedY = 2u, kAlignedTmp0 = 4u, kAlignedTmp1 = 8u;  // bit set: that buffer is 16-byte aligned
+
+static unsigned conv_alignment(const void* x, const void* y, const void* tmp0, const void* tmp1) {
+  auto ok = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  return (ok(x) ? kAlignedX : 0u) | (ok(y) ? kAlignedY : 0u) | (ok(tmp0) ? kAlignedTmp0 : 0u) | (ok(tmp1) ? kAlignedTmp1 : 0u);
+}
+
+// Returns the number of passes (1 .. 3; 0 when no radius is active), TIO_ERR_UNSUPPORTED_CONFIG when stages ride along
+// and the fused form does not exist for these arguments, TIO_ERR_INVALID_ARGUMENT when a pass does not fit one launch.
+static int plan_conv(int dt, int32_t batch, int32_t channels, const int32_t shape[3], const int32_t radius[3], unsigned aligned,
+                     bool has_skip, bool bias_on, int noise_on, bool fma, tio_conv_pass out[3]) {
   int active[3], n_active = 0;
   for (int ax = 0; ax < 3; ax++)
     if (radius[ax] > 0) active[n_active++] = ax;
-  const void* src = x;
+  const bool io_aligned = (aligned & (kAlignedX | kAlignedY | kAlignedTmp0)) == (kAlignedX | kAlignedY | kAlignedTmp0);
   // J and K can share one pass when the whole K row sits in one 256-wide tile and both radii
   // are small: the J kernel filters every row it produces along K before storing it
   // (only the 16-byte kernels have the fused K stage: with a pointer that keeps a pass off them — the gate of the loop
   // below — the K pass must stay in the plan, or nothing filters along K)
-  const bool fuse_jk = DT == TIO_F32 && radius[1] > 0 && radius[2] > 0 && radius[1] <= kConvMaxRadiusV4 && radius[2] <= 8 &&
-                       shape[2] <= 256 && (shape[2] & 3) == 0 && !env_switches().conv_no_fuse &&
-                       ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(tmp0)) & 15) == 0;
-  if (fuse.any()) {
+  const bool fuse_jk = dt == TIO_F32 && radius[1] > 0 && radius[2] > 0 && radius[1] <= kConvMaxRadiusV4 && radius[2] <= 8 &&
+                       shape[2] <= 256 && (shape[2] & 3) == 0 && !env_switches().conv_no_fuse && io_aligned;
+  if (bias_on || noise_on != 0) {
     // the pointwise stages ride on the marching I pass (loads) and the fused J+K pass (stores)
-    const bool ok = DT == TIO_F32 && n_active == 3 && fuse_jk && radius[0] <= kConvMaxRadiusV4 && skip == nullptr &&
-                    ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(tmp0)) & 15) == 0;
+    const bool ok = dt == TIO_F32 && n_active == 3 && fuse_jk && radius[0] <= kConvMaxRadiusV4 && !has_skip && io_aligned;
     if (!ok) return TIO_ERR_UNSUPPORTED_CONFIG;
   }
+  const int bcs = batch * channels;
+  int n_passes = 0;
+  unsigned src_bit = kAlignedX;
   for (int s = 0; s < n_active; s++) {
     const int axis = active[s];
     if (axis == 2 && fuse_jk) break;  // done by the J pass
     const bool first = s == 0, last = s == n_active - 1 || (axis == 1 && fuse_jk);
-    void* dst = last ? y : static_cast<void*>((s % 2 == 0) ? tmp0 : tmp1);
-    ConvArgs a{};
-    a.src = src; a.dst = dst; a.x_orig = x; a.taps = taps; a.skip = skip;
-    a.I = shape[0]; a.J = shape[1]; a.K = shape[2];
-    a.channels = channels; a.axis = axis; a.radius = radius[axis];
-    a.taps_batched = taps_batched; a.tap_stride = tap_stride; a.orig_dtype = DT; a.last_pass = last ? 1 : 0;
+    const unsigned dst_bit = last ? kAlignedY : ((s % 2 == 0) ? kAlignedTmp0 : kAlignedTmp1);
+    tio_conv_pass& p = out[n_passes++];
+    p = tio_conv_pass{};
+    p.axis = axis; p.radius = radius[axis]; p.last = last ? 1 : 0;
     const int ntaps = 2 * radius[axis] + 1;
-    const int bcs = batch * channels;
-    dim3 grid;
+    unsigned gx, gy, gz;
     size_t lds;
     if (axis == 2) {
-      grid = dim3((shape[2] + kConvKSpan - 1) / kConvKSpan, (shape[1] + 3) / 4, static_cast<unsigned>(shape[0]) * bcs);
+      p.family = TIO_CONV_K;
+      gx = (shape[2] + kConvKSpan - 1) / kConvKSpan; gy = (shape[1] + 3) / 4; gz = static_cast<unsigned>(shape[0]) * bcs;
       lds = (((ntaps + 3) & ~3) + 4 * (kConvKSpan + 2 * radius[axis])) * sizeof(float);
     } else {
       const int n = shape[axis], other = axis == 0 ? shape[1] : shape[0];
-      grid = dim3((shape[2] + 63) / 64, (n + kConvLine - 1) / kConvLine, static_cast<unsigned>(other) * bcs);
+      p.family = TIO_CONV_LINE;
+      gx = (shape[2] + 63) / 64; gy = (n + kConvLine - 1) / kConvLine; gz = static_cast<unsigned>(other) * bcs;
       lds = (((ntaps + 3) & ~3) + (kConvLine + 2 * radius[axis]) * 64) * sizeof(float);
+      p.segments = static_cast<int32_t>(gy); p.rows_per_segment = kConvLine;
     }
-    if (grid.z > 65535u || grid.y > 65535u) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_separable_conv3d: volume too large for one launch");
-#define TIO_CONV_LAUNCH(S, D)                                                                      \
-  do {                                                                                             \
-    if (axis == 2) hipLaunchKernelGGL((conv_k_kernel<S, D>), grid, dim3(kBlock), lds, stream, a);  \
-    else hipLaunchKernelGGL((conv_line_kernel<S, D>), grid, dim3(kBlock), lds, stream, a);         \
-  } while (0)
-    const bool f32_pass = (first ? DT == TIO_F32 : true) && (last ? DT == TIO_F32 : true);
-    const bool aligned = ((shape[2] & 3) == 0) && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) |
-                                                     reinterpret_cast<uintptr_t>(x)) & 15) == 0;
-    if (f32_pass && aligned && radius[axis] <= kConvMaxRadiusV4) {  // 16-byte access fast paths
+    // (the limit of the generic kernels' grid holds for every family: one rule, whatever the pointers' alignment)
+    if (gz > 65535u || gy > 65535u) return TIO_ERR_INVALID_ARGUMENT;
+    const bool f32_pass = (first ? dt == TIO_F32 : true) && (last ? dt == TIO_F32 : true);
+    const bool pass_aligned = ((shape[2] & 3) == 0) && (aligned & (src_bit | dst_bit | kAlignedX)) == (src_bit | dst_bit | kAlignedX);
+    if (f32_pass && pass_aligned && radius[axis] <= kConvMaxRadiusV4) {  // 16-byte access fast paths
       if (axis == 2) {
         const int r4 = std::max((radius[axis] + 3) & ~3, 8);
+        p.family = TIO_CONV_K_V4;
         lds = (((ntaps + 3) & ~3) + 4 * (2 * kConvKSpan + 2 * r4)) * sizeof(float);
-        grid.y = static_cast<unsigned>((shape[1] + 4 * kConvKRows - 1) / (4 * kConvKRows));
-        hipLaunchKernelGGL(conv_k_v4_kernel, grid, dim3(kBlock), lds, stream, a);
+        gy = static_cast<unsigned>((shape[1] + 4 * kConvKRows - 1) / (4 * kConvKRows));
       } else {
         // one or two marching segments per line: enough blocks to fill the chip, halo re-read only at the cut
         const int n = shape[axis], other = axis == 0 ? shape[1] : shape[0];
@@ -975,36 +983,82 @@ static int launch_conv(const void* x, void* y, float* tmp0, float* tmp1, int32_t
         int segs = lines >= 4096 ? 1 : (lines >= 2048 ? 2 : 4);
         int seg_len = ((n + segs - 1) / segs + kConvStep - 1) / kConvStep * kConvStep;
         segs = (n + seg_len - 1) / seg_len;
-        grid.x = static_cast<unsigned>((shape[2] + 255) / 256);
-        grid.y = static_cast<unsigned>(segs);
+        gx = static_cast<unsigned>((shape[2] + 255) / 256);
+        gy = static_cast<unsigned>(segs);
         const bool fused = axis == 1 && fuse_jk;
-        a.radius_k = fused ? radius[2] : 0;
-        const bool pre_bias = axis == 0 && fuse.bias_coarse != nullptr;
-        const bool post_noise = fused && fuse.noise_on != 0;
-        const bool noise_base = post_noise && fuse.noise_on == 2;
-        if (pre_bias) {
-          a.bias_coarse = fuse.bias_coarse;
-          a.bias_ci = fuse.bias_shape[0]; a.bias_cj = fuse.bias_shape[1]; a.bias_ck = fuse.bias_shape[2];
-          a.bias_si = lerp_scale(a.bias_ci, shape[0]); a.bias_sj = lerp_scale(a.bias_cj, shape[1]); a.bias_sk = lerp_scale(a.bias_ck, shape[2]);
-        }
-        if (post_noise) {
-          a.noise_on = fuse.noise_on; a.noise_base = fuse.noise_base; a.noise_batched = fuse.noise_batched; a.noise_mean = fuse.noise_mean; a.noise_std = fuse.noise_std;
-          a.noise_mean_b = fuse.noise_mean_b; a.noise_std_b = fuse.noise_std_b; a.noise_seed = fuse.noise_seed;
-        }
+        p.radius_k = fused ? radius[2] : 0;
+        p.pre_bias = (axis == 0 && bias_on) ? 1 : 0;
+        p.post_noise = fused ? noise_on : 0;
         // (the bias variant needs > 240 VGPRs beyond radius 6: the LDS ring kernel is the better choice there)
-        if (radius[axis] <= (pre_bias ? 6 : kMarchMaxRadius) && !env_switches().conv_ring) {
+        if (radius[axis] <= (p.pre_bias ? 6 : kMarchMaxRadius) && !env_switches().conv_ring) {
           // register-window marching: one strip per wave, enough segments for >= 8 waves per SIMD
-          a.bcs = bcs;
-          a.fma = fuse.fma;
+          p.family = TIO_CONV_MARCH;
+          p.radius_class = std::min(radius[axis], kMarchMaxRadius);
+          p.fma = fma ? 1 : 0;
           const int64_t strips = lines;
           int want = static_cast<int>((8192 + strips - 1) / strips);
           want = std::max(1, std::min(want, std::max(1, n / 32)));
           const int len = (n + want - 1) / want;
-          grid.y = static_cast<unsigned>((n + len - 1) / len);
-          grid.z = static_cast<unsigned>((static_cast<int64_t>(other) * bcs + kBlock / 64 - 1) / (kBlock / 64));
+          gy = static_cast<unsigned>((n + len - 1) / len);
+          gz = static_cast<unsigned>((static_cast<int64_t>(other) * bcs + kBlock / 64 - 1) / (kBlock / 64));
           lds = fused ? 4 * 272 * sizeof(float) : 0;
-          a.tiles_a = 0;
-          if (a.tiles_a) std::swap(grid.x, grid.z);
+        } else {
+          p.family = TIO_CONV_RING;
+          lds = (((ntaps + 3) & ~3) + (2 * kConvStep + 2 * radius[axis]) * 256 + (fused ? 4 * 272 : 0)) * sizeof(float);
+        }
+        // the kernels cut the line themselves, into gridDim.y segments of ceil(n / gridDim.y) rows
+        p.segments = static_cast<int32_t>(gy);
+        p.rows_per_segment = static_cast<int32_t>((n + gy - 1) / gy);
+      }
+    }
+    p.grid[0] = static_cast<int32_t>(gx); p.grid[1] = static_cast<int32_t>(gy); p.grid[2] = static_cast<int32_t>(gz);
+    p.k_tiles = static_cast<int32_t>(gx);
+    p.lds_bytes = static_cast<int32_t>(lds);
+    src_bit = dst_bit;
+  }
+  return n_passes;
+}
+
+template <int DT>
+static int launch_conv(const void* x, void* y, float* tmp0, float* tmp1, int32_t batch, int32_t channels,
+                       const int32_t shape[3], const float* taps, int taps_batched, int tap_stride,
+                       const int32_t radius[3], const uint8_t* skip, hipStream_t stream, const ConvFuse& fuse = ConvFuse()) {
+  tio_conv_pass passes[3];
+  const int n_passes = plan_conv(DT, batch, channels, shape, radius, conv_alignment(x, y, tmp0, tmp1), skip != nullptr,
+                                 fuse.bias_coarse != nullptr, fuse.noise_on, fuse.fma != 0, passes);
+  if (n_passes == TIO_ERR_INVALID_ARGUMENT) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_separable_conv3d: volume too large for one launch");
+  if (n_passes < 0) return n_passes;
+  const void* src = x;
+  for (int s = 0; s < n_passes; s++) {
+    const tio_conv_pass& p = passes[s];
+    const int axis = p.axis;
+    const bool first = s == 0, last = p.last != 0;
+    void* dst = last ? y : static_cast<void*>((s % 2 == 0) ? tmp0 : tmp1);
+    ConvArgs a{};
+    a.src = src; a.dst = dst; a.x_orig = x; a.taps = taps; a.skip = skip;
+    a.I = shape[0]; a.J = shape[1]; a.K = shape[2];
+    a.channels = channels; a.axis = axis; a.radius = p.radius;
+    a.taps_batched = taps_batched; a.tap_stride = tap_stride; a.orig_dtype = DT; a.last_pass = last ? 1 : 0;
+    a.radius_k = p.radius_k;
+    const dim3 grid(static_cast<unsigned>(p.grid[0]), static_cast<unsigned>(p.grid[1]), static_cast<unsigned>(p.grid[2]));
+    const size_t lds = static_cast<size_t>(p.lds_bytes);
+    const bool fused = p.radius_k > 0, pre_bias = p.pre_bias != 0, post_noise = p.post_noise != 0, noise_base = p.post_noise == 2;
+    if (pre_bias) {
+      a.bias_coarse = fuse.bias_coarse;
+      a.bias_ci = fuse.bias_shape[0]; a.bias_cj = fuse.bias_shape[1]; a.bias_ck = fuse.bias_shape[2];
+      a.bias_si = lerp_scale(a.bias_ci, shape[0]); a.bias_sj = lerp_scale(a.bias_cj, shape[1]); a.bias_sk = lerp_scale(a.bias_ck, shape[2]);
+    }
+    if (post_noise) {
+      a.noise_on = fuse.noise_on; a.noise_base = fuse.noise_base; a.noise_batched = fuse.noise_batched; a.noise_mean = fuse.noise_mean; a.noise_std = fuse.noise_std;
+      a.noise_mean_b = fuse.noise_mean_b; a.noise_std_b = fuse.noise_std_b; a.noise_seed = fuse.noise_seed;
+    }
+    switch (p.family) {
+      case TIO_CONV_K_V4:
+        hipLaunchKernelGGL(conv_k_v4_kernel, grid, dim3(kBlock), lds, stream, a);
+        break;
+      case TIO_CONV_MARCH: {
+        a.bcs = batch * channels;
+        a.fma = p.fma;
 #define TIO_MARCH_VARIANT_F(RR, FM)                                                                                                  \
   {                                                                                                                                  \
     if (fused && noise_base) hipLaunchKernelGGL((conv_march_kernel<RR, true, false, 2, FM>), grid, dim3(kBlock), lds, stream, a);     \
@@ -1015,24 +1069,23 @@ static int launch_conv(const void* x, void* y, float* tmp0, float* tmp1, int32_t
   }
 #define TIO_MARCH_VARIANT(RR)                                                                              \
   {                                                                                                        \
-    if (fuse.fma) { TIO_MARCH_VARIANT_F(RR, true) } else { TIO_MARCH_VARIANT_F(RR, false) }                                      \
+    if (p.fma) { TIO_MARCH_VARIANT_F(RR, true) } else { TIO_MARCH_VARIANT_F(RR, false) }                                         \
   }
-          switch (radius[axis]) {
-            case 1: TIO_MARCH_VARIANT(1) break;
-            case 2: TIO_MARCH_VARIANT(2) break;
-            case 3: TIO_MARCH_VARIANT(3) break;
-            case 4: TIO_MARCH_VARIANT(4) break;
-            case 5: TIO_MARCH_VARIANT(5) break;
-            case 6: TIO_MARCH_VARIANT(6) break;
-            case 7: TIO_MARCH_VARIANT(7) break;
-            default: TIO_MARCH_VARIANT(8) break;
-          }
+        switch (p.radius_class) {
+          case 1: TIO_MARCH_VARIANT(1) break;
+          case 2: TIO_MARCH_VARIANT(2) break;
+          case 3: TIO_MARCH_VARIANT(3) break;
+          case 4: TIO_MARCH_VARIANT(4) break;
+          case 5: TIO_MARCH_VARIANT(5) break;
+          case 6: TIO_MARCH_VARIANT(6) break;
+          case 7: TIO_MARCH_VARIANT(7) break;
+          default: TIO_MARCH_VARIANT(8) break;
+        }
 #undef TIO_MARCH_VARIANT
 #undef TIO_MARCH_VARIANT_F
-          src = dst;
-          continue;
-        }
-        lds = (((ntaps + 3) & ~3) + (2 * kConvStep + 2 * radius[axis]) * 256 + (fused ? 4 * 272 : 0)) * sizeof(float);
+        break;
+      }
+      case TIO_CONV_RING: {
 #define TIO_LINE_LAUNCH(FK, PB, PN)                                                                                   \
   {                                                                                                                   \
     auto kern = conv_line_v4_kernel<FK, PB, PN>;                                                                      \
@@ -1047,15 +1100,22 @@ static int launch_conv(const void* x, void* y, float* tmp0, float* tmp1, int32_t
         else if (pre_bias) TIO_LINE_LAUNCH(false, true, 0)
         else TIO_LINE_LAUNCH(false, false, 0)
 #undef TIO_LINE_LAUNCH
+        break;
       }
-      src = dst;
-      continue;
-    }
-    if (first && last) TIO_CONV_LAUNCH(DT, DT);
-    else if (first) TIO_CONV_LAUNCH(DT, TIO_F32);
-    else if (last) TIO_CONV_LAUNCH(TIO_F32, DT);
-    else TIO_CONV_LAUNCH(TIO_F32, TIO_F32);
+      default: {  // the generic kernels: any dtype, any alignment
+#define TIO_CONV_LAUNCH(S, D)                                                                      \
+  do {                                                                                             \
+    if (axis == 2) hipLaunchKernelGGL((conv_k_kernel<S, D>), grid, dim3(kBlock), lds, stream, a);  \
+    else hipLaunchKernelGGL((conv_line_kernel<S, D>), grid, dim3(kBlock), lds, stream, a);         \
+  } while (0)
+        if (first && last) TIO_CONV_LAUNCH(DT, DT);
+        else if (first) TIO_CONV_LAUNCH(DT, TIO_F32);
+        else if (last) TIO_CONV_LAUNCH(TIO_F32, DT);
+        else TIO_CONV_LAUNCH(TIO_F32, TIO_F32);
 #undef TIO_CONV_LAUNCH
+        break;
+      }
+    }
     src = dst;
   }
   return check_launch("tio_separable_conv3d");
@@ -1456,6 +1516,27 @@ extern "C" int tio_separable_conv3d(const void* x, void* y, void* tmp, int32_t d
   TIO_DISPATCH_FLOAT(dtype, TIO_CONV)
 #undef TIO_CONV
   return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_separable_conv3d: dtype %d", dtype);
+}
+
+extern "C" int tio_separable_conv3d_passes(int32_t dtype, int32_t batch, int32_t channels, const int32_t shape[3],
+                                           const int32_t radius[3], int32_t aligned16, int32_t has_skip, int32_t bias_on,
+                                           int32_t noise_on, int32_t fast_math, tio_conv_pass out_passes[3]) {
+  if (shape == nullptr || radius == nullptr || out_passes == nullptr)
+    return fail(TIO_ERR_INVALID_ARGUMENT, "tio_separable_conv3d_passes: null argument");
+  if (!is_float_dtype(dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_separable_conv3d_passes: dtype %d", dtype);
+  if (batch < 0 || channels < 1 || shape[0] < 1 || shape[1] < 1 || shape[2] < 1)
+    return fail(TIO_ERR_INVALID_ARGUMENT, "tio_separable_conv3d_passes: bad shape");
+  for (int a = 0; a < 3; a++)
+    if (radius[a] < 0 || radius[a] > kMaxRadius)
+      return fail(TIO_ERR_INVALID_ARGUMENT, "tio_separable_conv3d_passes: radius[%d]=%d is not in 0 .. %d", a, radius[a], kMaxRadius);
+  if (noise_on < 0 || noise_on > 2) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_separable_conv3d_passes: noise_on must be 0, 1 or 2");
+  if (batch == 0) return 0;
+  const bool stages = bias_on != 0 || noise_on != 0 || fast_math != 0;  // the caller asks about tio_blur_fused
+  if (stages && (dtype != TIO_F32 || aligned16 == 0)) return TIO_ERR_UNSUPPORTED_CONFIG;
+  const unsigned aligned = aligned16 != 0 ? (kAlignedX | kAlignedY | kAlignedTmp0 | kAlignedTmp1) : 0u;
+  const int n_passes = plan_conv(dtype, batch, channels, shape, radius, aligned, has_skip != 0, bias_on != 0, noise_on, fast_math != 0, out_passes);
+  if (n_passes == TIO_ERR_INVALID_ARGUMENT) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_separable_conv3d_passes: volume too large for one launch");
+  return n_passes;
 }
 
 // =============================================================================
