@@ -611,6 +611,32 @@ int tio_keep_largest_component(const void* x, void* y, int32_t dtype, int32_t ba
                                int32_t fully_connected, void* workspace_dev, int64_t workspace_bytes,
                                void* stream);
 
+/*
+ * LabelsToImage (labels_to_image.py:182-218 _generate_per_element, :263-290 _generate_from_labels: PER LABEL a full-volume
+ * randn_like, a multiply, an add, a `==` mask, a cast, another multiply and an accumulate) as one pass: the masks
+ * `label == v` are disjoint, so every voxel gets one Gaussian draw with the mean and the deviation of its own label.
+ * Additive to ABI 18; no CPU restatement.
+ *   labels       (batch, channels, n_spatial) of any tio_dtype; only channel 0 of each element is read (`label_data[:, 0:1]`)
+ *   out          (batch, 1, n_spatial) float32, must not overlap `labels` (nor `base_dev`)
+ *   keys_dev     device, n_keys <= TIO_REMAP_MAX_PAIRS doubles, strictly ASCENDING (as tio_label_remap)
+ *   mean_dev, std_dev   device, n_keys floats each, or batch * n_keys (element-major) when params_batched
+ * A voxel whose value is no key (the reference takes its keys from element 0 alone; a non-integer value of a floating map)
+ * is written as +0.0f; so is one whose key has mean and deviation both zero (the reference's `continue`).
+ *
+ * Fused mode (base_dev == NULL): out[b, v] = fadd(mean[k], fmul(std[k], z)), two separately rounded float32 operations, z
+ * the standard normal tio_philox_normal(out, batch * n_spatial, philox_seed, 0) puts at flat index b * n_spatial + v.
+ * One-label mode (base_dev != NULL: batch * n_spatial standard normals of the caller): only key index base_key is
+ * looked at.  Where the label equals keys[base_key] the call writes fadd(fadd(fmul(base, std), mean), +0.0f) — the
+ * reference's `randn * std + mean`, `* mask`, `result +=` onto zeros — and every other voxel keeps what `out` holds: the
+ * caller clears `out` once and calls once per label, in the reference's loop order, with the reference's own draws.
+ * 8-bit labels: a 256-entry table in LDS; other dtypes: a binary search in the keys, from LDS up to 2048 of them.
+ * batch > 65535: TIO_ERR_UNSUPPORTED_CONFIG.  batch == 0 or n_spatial == 0: TIO_OK, nothing done.
+ */
+int tio_labels_to_image(const void* labels, int32_t dtype, int32_t batch, int32_t channels, int64_t n_spatial,
+                        const double* keys_dev, int32_t n_keys, const float* mean_dev, const float* std_dev,
+                        int32_t params_batched, float* out, uint64_t philox_seed, const float* base_dev,
+                        int32_t base_key, void* stream);
+
 /* ------------------------------------------------------------------------ */
 /* Intensity preprocessing with on-device statistics (ABI 17, additive)      */
 /* ------------------------------------------------------------------------ */

@@ -64,10 +64,10 @@ def install_alias() -> None:
 
         return type(name, (torchio_amd.transforms.Transform,), {"__init__": __init__, "forward": skip, "make_params": skip})
 
-    # Ghosting, Spike and Swap exist in the package, but this run computes on the CPU oracle, which has no counterpart of
-    # their HIP-only entry points (those are checked on the GPU, tests/test_gpu_kspace_artefacts.py and
-    # tests/test_gpu_swap_histogram.py): the placeholders stay whatever is exported
-    for hip_only in ("Ghosting", "Spike", "Swap"):
+    # Ghosting, Spike, Swap and LabelsToImage exist in the package, but this run computes on the CPU oracle, which has no
+    # counterpart of their HIP-only entry points (those are checked on the GPU, tests/test_gpu_kspace_artefacts.py,
+    # tests/test_gpu_swap_histogram.py and tests/test_gpu_labels_to_image.py): the placeholders stay whatever is exported
+    for hip_only in ("Ghosting", "Spike", "Swap", "LabelsToImage"):
         setattr(torchio_amd, hip_only, _placeholder(hip_only))
 
     # the reference keeps its spatial transforms in a package (torchio.transforms.spatial.spatial); private helpers

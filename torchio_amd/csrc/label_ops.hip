@@ -6,35 +6,10 @@
 //   tio_keep_largest_component  KeepLargestComponent: connected components of all listed labels at once, on the device
 //                               (the reference copies one mask per label and element to the host for SimpleITK).
 #include "common.hpp"
+#include "label_keys.hpp"
 
 namespace tio {
 namespace {
-
-// ---- element <-> double (the comparisons of the reference are `data == python_int`: exact in double for every dtype
-// but int64 beyond 2^53) ---------------------------------------------------------------------------------------------
-template <int DT>
-struct Lab {
-  using T = typename Elem<DT>::type;
-  static __device__ __forceinline__ double to_double(T v) { return static_cast<double>(v); }
-  static __device__ __forceinline__ T from_double(double d) { return static_cast<T>(d); }
-};
-template <>
-struct Lab<TIO_BF16> {
-  using T = uint16_t;
-  static __device__ __forceinline__ double to_double(T v) { return static_cast<double>(bf16_bits_to_float(v)); }
-  static __device__ __forceinline__ T from_double(double d) { return float_to_bf16_bits(static_cast<float>(d)); }
-};
-
-// first index whose key is not below v, then the equality: -1 when v is no key (NaN compares false everywhere: -1)
-__device__ __forceinline__ int find_key(const double* keys, int n, double v) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (keys[mid] < v) lo = mid + 1;
-    else hi = mid;
-  }
-  return (lo < n && keys[lo] == v) ? lo : -1;
-}
 
 // y[i] = f(x[i]) with 16-byte loads and stores wherever x and y share their offset from a 16-byte boundary (the
 // elements in front of the first boundary and behind the last whole vector go one by one); x == y is allowed: every

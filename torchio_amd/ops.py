@@ -1628,6 +1628,64 @@ class Engine:
             result = out if result is None else torch.where(out != data, out, result)
         return result
 
+    # -- LabelsToImage (transforms/intensity/labels_to_image.py) ---------------------------------------------------------
+    def labels_to_image(self, labels: Tensor, keys, means, stds, *, seed: int | None = None, base: Tensor | None = None,
+                        base_key: int | None = None, out: Tensor | None = None) -> Tensor:
+        """The synthetic float32 ``(B, 1, I, J, K)`` image of a ``(B, C, I, J, K)`` label map (channel 0 is read).
+
+        ``keys``: the label values, strictly ascending; ``means`` / ``stds``: one value per key, or ``(B, len(keys))`` of
+        them for per-element parameters.  A voxel whose label is no key becomes 0.
+
+        Fused mode (``seed``): one launch, ``mean + std * z`` with ``z = philox_normal(out.shape, seed, 0)``.
+        One-label mode (``base``, ``base_key``): only ``keys[base_key]`` is looked at; its voxels become
+        ``base * std + mean`` with the caller's float32 normals ``base`` (shaped like the result), every other voxel keeps
+        what ``out`` holds (``out=None``: zeros).  Called once per label with ``torch.randn`` draws this is the reference.
+        """
+        what = "labels_to_image"
+        if labels.ndim != 5:
+            raise ValueError(f"{what}: expected a (B, C, I, J, K) tensor, got {tuple(labels.shape)}")
+        if (seed is None) == (base is None):
+            raise ValueError(f"{what}: give either seed (fused mode) or base and base_key (one-label mode)")
+        batch, channels = int(labels.shape[0]), int(labels.shape[1])
+        keys_t = keys.detach().to(torch.float64).reshape(-1) if isinstance(keys, Tensor) else torch.tensor([float(k) for k in keys], dtype=torch.float64)
+        n_keys = keys_t.numel()
+        if n_keys > _abi.REMAP_MAX_PAIRS:
+            raise ValueError(f"{what}: at most {_abi.REMAP_MAX_PAIRS} keys, got {n_keys}")
+        if n_keys > 1 and not bool((keys_t[1:] > keys_t[:-1]).all()):  # (keys on the device: one read-back)
+            raise ValueError(f"{what}: the keys must be strictly ascending")
+        mean_t, std_t = (torch.as_tensor(v, dtype=torch.float32) for v in (means, stds))
+        if mean_t.shape != std_t.shape or tuple(mean_t.shape) not in ((n_keys,), (batch, n_keys)):
+            raise ValueError(f"{what}: means {tuple(mean_t.shape)} and stds {tuple(std_t.shape)} for {n_keys} keys and a batch of {batch}")
+        batched = mean_t.ndim == 2
+        result_shape = (batch, 1, *labels.shape[2:])
+        if base is not None:
+            if base_key is None or not 0 <= int(base_key) < n_keys:
+                raise ValueError(f"{what}: base_key {base_key!r} outside [0, {n_keys})")
+            if tuple(base.shape) != result_shape or base.dtype != torch.float32:
+                raise ValueError(f"{what}: base must be float32 of shape {result_shape}")
+            base = base.contiguous()
+        if out is not None:
+            if base is None:
+                raise ValueError(f"{what}: out is reused in one-label mode only")
+            if tuple(out.shape) != result_shape or out.dtype != torch.float32 or not out.is_contiguous():
+                raise ValueError(f"{what}: out must be contiguous float32 of shape {result_shape}")
+        labels = labels.contiguous()
+        device = labels.device
+        # (the doubles travel as pairs of float32 words: one staging copy for the three blocks)
+        keys_dev, mean_dev, std_dev = h2d_packed([keys_t.contiguous().view(torch.float32) if keys_t.device.type == "cpu" else keys_t, mean_t.contiguous(), std_t.contiguous()], device)
+        if keys_dev.dtype != torch.float64:
+            keys_dev = keys_dev.view(torch.float64)
+        self._check(what, labels, keys_dev, mean_dev, std_dev, base, out)
+        if out is None:
+            out = torch.empty(result_shape, dtype=torch.float32, device=device)
+            if base is not None:
+                out.zero_()
+        n_spatial = labels[0, 0].numel() if batch and channels else 0
+        self._call(what, labels, _ptr(labels), dtype_code(labels.dtype), batch, channels, n_spatial, _ptr(keys_dev), n_keys, _ptr(mean_dev),
+                   _ptr(std_dev), int(batched), _ptr(out), (int(seed) if seed is not None else 0) & (2**64 - 1), _ptr(base),
+                   int(base_key) if base is not None else 0, self._stream(labels))
+        return out
+
     # -- intensity preprocessing with on-device statistics (normalize.py, standardize.py, clamp.py, mask.py) -------------
     _MAP_MODES = {"rescale_clip": _abi.MAP_RESCALE_CLIP, "rescale": _abi.MAP_RESCALE, "sub_div": _abi.MAP_SUB_DIV, "mul_add": _abi.MAP_MUL_ADD}
 

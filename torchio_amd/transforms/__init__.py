@@ -16,6 +16,7 @@ from .labels import OneHot
 from .labels import RemapLabels
 from .labels import RemoveLabels
 from .labels import SequentialLabels
+from .labels_to_image import LabelsToImage
 from .motion import Motion
 from .noise import Noise
 from .noise import get_noise_rng
@@ -43,7 +44,7 @@ from .transform import Transform
 
 __all__ = [
     "Affine", "Anisotropy", "AppliedTransform", "BiasField", "Blur", "Choice", "Clamp", "Compose", "Contour", "Crop", "ElasticDeformation", "Flip", "Gamma", "Ghosting",
-    "HistogramStandardization", "IntensityTransform", "KeepLargestComponent", "Mask", "Motion", "Noise", "Normalize", "OneHot", "OneOf", "Pad", "RemapLabels", "RemoveLabels", "Resample", "RescaleIntensity",
+    "HistogramStandardization", "IntensityTransform", "KeepLargestComponent", "LabelsToImage", "Mask", "Motion", "Noise", "Normalize", "OneHot", "OneOf", "Pad", "RemapLabels", "RemoveLabels", "Resample", "RescaleIntensity",
     "Resize", "SequentialLabels", "SomeOf", "Spatial", "SpatialTransform", "Spike", "Standardize", "Swap", "Transform", "ZNormalization",
     "apply_inverse_transform", "get_inverse_transform", "get_noise_rng", "set_noise_rng",
 ]
