@@ -473,6 +473,21 @@ int tio_axis_gather_lerp(const void* x, void* y, int32_t dtype, int32_t batch, i
 int tio_flip3d(const void* x, void* y, int32_t dtype, int32_t batch, int32_t channels,
                const int32_t shape[3], int32_t axes_mask, const uint8_t* flags_dev, void* stream);
 
+/*
+ * Reorient (transforms/spatial/reorient.py:63-91 _apply_reorientation: up to three torch.flip
+ * passes, then permute(...).contiguous()) and Transpose (transforms/spatial/transpose.py:44:
+ * permute(0, 1, 4, 3, 2).contiguous()) as one element move.  Additive to ABI 18, HIP only.
+ *   y is (B, C, in_shape[perm[0]], in_shape[perm[1]], in_shape[perm[2]]);
+ *   y[b, c, o0, o1, o2] = x[b, c, i0, i1, i2] with i[perm[d]] = o_d, or in_shape[perm[d]] - 1 - o_d
+ *   when bit perm[d] of flip_mask is set: nibabel's apply_orientation order (flip the input axes,
+ *   then transpose by perm = argsort(ornt[:, 0])).
+ * Every dtype (dispatch on the element size).  perm[2] == 2 keeps rows along K (a grid-stride
+ * move); any other perm goes through a 64 x 64 LDS tile so that reads and writes are both
+ * coalesced.  x and y must not overlap.
+ */
+int tio_permute3d(const void* x, void* y, int32_t dtype, int32_t batch, int32_t channels,
+                  const int32_t in_shape[3], const int32_t perm[3], int32_t flip_mask, void* stream);
+
 typedef enum tio_pad_mode {
   TIO_PAD_CONSTANT = 0,  /* F.pad(mode="constant", value=fill); also the statistic modes (per-element constants) */
   TIO_PAD_REFLECT = 1,   /* F.pad(mode="reflect"): mirror without repeating the edge                              */

@@ -13,6 +13,7 @@ summary at the end is what `tests/REFERENCE_TESTS.md` records.
 from __future__ import annotations
 
 import importlib
+import importlib.util
 import os
 import pkgutil
 import re
@@ -26,6 +27,7 @@ DEFAULT_FILES = [
     "test_blur.py", "test_gamma.py", "test_noise.py", "test_bias_field.py", "test_motion.py", "test_spatial.py", "test_resize.py", "test_anisotropy.py",
     "test_flip.py", "test_pad.py", "test_crop.py", "test_compose.py", "test_one_of.py", "test_some_of.py", "test_inverse.py", "test_parameter_range.py",
     "test_patches.py", "test_queue.py", "test_affine.py", "test_batch.py", "test_per_instance.py", "test_vectorization.py",
+    "test_crop_or_pad.py", "test_ensure_shape_multiple.py", "test_to_reference_space.py", "test_copy_affine.py",
 ]
 
 
@@ -44,6 +46,10 @@ def install_alias() -> None:
     from torchio_amd import ops  # noqa: PLC0415
 
     ops._ENGINE = oracle_engine()
+    if importlib.util.find_spec("nibabel") is None:
+        # test_crop_or_pad.py imports nibabel at the top and uses it in its file-backed tests only (out of scope: they fail
+        # on the empty module); without the name the whole file would not be collected
+        sys.modules["nibabel"] = types.ModuleType("nibabel")
     sys.modules["torchio"] = torchio_amd
     for info in pkgutil.walk_packages(torchio_amd.__path__, "torchio_amd."):
         module = importlib.import_module(info.name)
@@ -66,8 +72,10 @@ def install_alias() -> None:
 
     # Ghosting, Spike, Swap and LabelsToImage exist in the package, but this run computes on the CPU oracle, which has no
     # counterpart of their HIP-only entry points (those are checked on the GPU, tests/test_gpu_kspace_artefacts.py,
-    # tests/test_gpu_swap_histogram.py and tests/test_gpu_labels_to_image.py): the placeholders stay whatever is exported
-    for hip_only in ("Ghosting", "Spike", "Swap", "LabelsToImage"):
+    # tests/test_gpu_swap_histogram.py and tests/test_gpu_labels_to_image.py): the placeholders stay whatever is exported.
+    # Reorient and Transpose move their voxels with tio_permute3d, HIP-only as well (tests/test_gpu_orientation.py), and
+    # the reference's test_reorient.py needs the real nibabel.
+    for hip_only in ("Ghosting", "Spike", "Swap", "LabelsToImage", "Reorient", "Transpose"):
         setattr(torchio_amd, hip_only, _placeholder(hip_only))
 
     # the reference keeps its spatial transforms in a package (torchio.transforms.spatial.spatial); private helpers
@@ -94,6 +102,9 @@ def install_alias() -> None:
         sys.modules[f"torchio.transforms.spatial.{name}"] = importlib.import_module(f"torchio_amd.transforms.{name}")
     sys.modules["torchio.transforms.spatial.crop"] = sys.modules["torchio.transforms.spatial.pad"]  # Pad and Crop share a module
     sys.modules["torchio.transforms.spatial._padding"] = sys.modules["torchio.transforms.spatial.pad"]
+    orientation = importlib.import_module("torchio_amd.transforms.orientation")  # six classes of the spatial package, one module here
+    for name in ("crop_or_pad", "ensure_shape_multiple", "to_reference_space", "copy_affine", "reorient", "transpose"):
+        sys.modules[f"torchio.transforms.spatial.{name}"] = orientation
 
 
 def install_binding() -> None:

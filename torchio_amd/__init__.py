@@ -40,7 +40,13 @@ from .transforms import Choice
 from .loader import ImagesLoader
 from .loader import SubjectsLoader
 from .transforms import Compose
+from .transforms import CopyAffine
 from .transforms import Crop
+from .transforms import CropOrPad
+from .transforms import EnsureShapeMultiple
+from .transforms import Reorient
+from .transforms import ToReferenceSpace
+from .transforms import Transpose
 from .transforms import Pad
 from .transforms import ElasticDeformation
 from .transforms import Flip
@@ -80,8 +86,8 @@ from .transforms import set_noise_rng
 __version__ = "0.1.0"
 
 __all__ = [
-    "Affine", "AffineMatrix", "Anisotropy", "AppliedTransform", "BiasField", "Blur", "Choice", "Clamp", "Compose", "Contour", "Crop", "ElasticDeformation", "Flip",
+    "Affine", "AffineMatrix", "Anisotropy", "AppliedTransform", "BiasField", "Blur", "Choice", "Clamp", "Compose", "Contour", "CopyAffine", "Crop", "CropOrPad", "ElasticDeformation", "EnsureShapeMultiple", "Flip",
     "Gamma", "Ghosting", "GridSampler", "HistogramStandardization", "Image", "ImagesBatch", "ImagesLoader", "IntensityTransform", "KeepLargestComponent", "LabelMap", "LabelSampler", "LabelsToImage", "Mask", "Motion", "Noise", "Normalize", "OneHot", "OneOf",
-    "Pad", "PatchAggregator", "PatchLocation", "PatchSampler", "Queue", "RemapLabels", "RemoveLabels", "Resample", "RescaleIntensity", "Resize", "ScalarImage", "SequentialLabels", "SomeOf", "Spatial", "SpatialTransform", "Spike", "Standardize", "Subject", "Swap",
-    "SubjectsBatch", "SubjectsLoader", "Transform", "UniformSampler", "WeightedSampler", "ZNormalization", "apply_inverse_transform", "calibrate_draw_policy", "get_draw_policy", "set_draw_policy", "get_noise_plan", "set_noise_plan", "get_inverse_transform", "get_noise_rng", "get_resample_precision", "get_stencil_precision", "set_noise_rng", "set_resample_precision", "set_stencil_precision",
+    "Pad", "PatchAggregator", "PatchLocation", "PatchSampler", "Queue", "RemapLabels", "RemoveLabels", "Reorient", "Resample", "RescaleIntensity", "Resize", "ScalarImage", "SequentialLabels", "SomeOf", "Spatial", "SpatialTransform", "Spike", "Standardize", "Subject", "Swap",
+    "SubjectsBatch", "SubjectsLoader", "ToReferenceSpace", "Transform", "Transpose", "UniformSampler", "WeightedSampler", "ZNormalization", "apply_inverse_transform", "calibrate_draw_policy", "get_draw_policy", "set_draw_policy", "get_noise_plan", "set_noise_plan", "get_inverse_transform", "get_noise_rng", "get_resample_precision", "get_stencil_precision", "set_noise_rng", "set_resample_precision", "set_stencil_precision",
 ]

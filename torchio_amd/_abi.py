@@ -270,6 +270,8 @@ HIP_ONLY_PROTOTYPES = {
         [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
          C.c_uint64, C.c_void_p, C.c_int32, C.c_void_p],
     ),
+    # Reorient / Transpose: the tiled axis permutation (additive to ABI 18): no CPU restatement either
+    "permute3d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _I32x3, _I32x3, C.c_int32, C.c_void_p]),
 }
 MULTI_QUANTILE_MAX_FRACTIONS = 32
 

@@ -202,3 +202,77 @@ class AffineMatrix:
         sp = ", ".join(f"{s:.2f}" for s in self.spacing)
         o = ", ".join(f"{v:.2f}" for v in self.origin)
         return f"AffineMatrix(spacing=({sp}), origin=({o}))"
+
+
+# -- orientation algebra ------------------------------------------------------------------------------------------------
+# The four nibabel functions ``Reorient`` calls (reference transforms/spatial/reorient.py:48-60, :161), restated from the
+# published algorithms like ``AffineMatrix.orientation`` above.  An "ornt" is a (3, 2) float array: row = voxel axis,
+# column 0 = the world (or output) axis it is closest to, column 1 = +1 / -1 for the direction along it.
+_AXIS_LABELS = (("L", "R"), ("P", "A"), ("I", "S"))
+
+
+def io_orientation(affine) -> np.ndarray:
+    """Orientation of the voxel axes of *affine* relative to world RAS+ (``nibabel.orientations.io_orientation``)."""
+    block = np.asarray(affine, dtype=np.float64)[:3, :3]
+    zooms = np.sqrt(np.sum(block * block, axis=0))
+    zooms[zooms == 0] = 1.0
+    left, singular, right = np.linalg.svd(block / zooms, full_matrices=False)
+    keep = singular > singular.max() * 3 * np.finfo(singular.dtype).eps
+    rotation = left[:, keep] @ right[keep]
+    ornt = np.full((3, 2), np.nan)
+    for axis in range(3):
+        column = rotation[:, axis]
+        if np.allclose(column, 0):
+            continue
+        world = int(np.argmax(np.abs(column)))
+        ornt[axis] = (world, -1.0 if column[world] < 0 else 1.0)
+        rotation[world, :] = 0  # a world axis is assigned once
+    return ornt
+
+
+def axcodes2ornt(axcodes) -> np.ndarray:
+    """Orientation array of axis codes such as ``('L', 'P', 'S')`` (``nibabel.orientations.axcodes2ornt``)."""
+    allowed = {code for pair in _AXIS_LABELS for code in pair} | {None}
+    if not set(axcodes).issubset(allowed):
+        raise ValueError(f"Not all axis codes {list(axcodes)} in label set {sorted(c for c in allowed if c)}")
+    ornt = np.full((len(axcodes), 2), np.nan)
+    for index, code in enumerate(axcodes):
+        for world, pair in enumerate(_AXIS_LABELS):
+            if code is not None and code in pair:
+                ornt[index] = (world, -1.0 if code == pair[0] else 1.0)
+                break
+    return ornt
+
+
+def ornt_transform(start_ornt, end_ornt) -> np.ndarray:
+    """The orientation that takes an array in *start_ornt* to *end_ornt* (``nibabel.orientations.ornt_transform``):
+    row = axis of the start array, column 0 = the axis of the end array it becomes, column 1 = -1 when it is reversed."""
+    start_ornt, end_ornt = np.asarray(start_ornt), np.asarray(end_ornt)
+    if start_ornt.shape != end_ornt.shape:
+        raise ValueError("The orientations must have the same shape")
+    if start_ornt.shape[1] != 2:
+        raise ValueError(f"Invalid shape for an orientation: {start_ornt.shape}")
+    result = np.empty_like(start_ornt)
+    for end_axis, (end_world, end_flip) in enumerate(end_ornt):
+        for start_axis, (start_world, start_flip) in enumerate(start_ornt):
+            if end_world == start_world:
+                result[start_axis] = (end_axis, 1 if start_flip == end_flip else -1)
+                break
+        else:
+            raise ValueError(f"Unable to find out axis {end_world} in start_ornt")
+    return result
+
+
+def inv_ornt_aff(ornt, shape) -> np.ndarray:
+    """The 4x4 that maps voxel indices of the REORIENTED array to indices of the array of *shape* it was made from
+    (``nibabel.orientations.inv_ornt_aff``): undo the axis order, then undo the flips about the array centre."""
+    ornt = np.asarray(ornt, dtype=np.float64)
+    if np.any(np.isnan(ornt)):
+        raise ValueError("We cannot invert orientation transformations that drop axes")
+    size = ornt.shape[0]
+    extent = np.array(shape, dtype=np.float64)[:size]
+    undo_reorder = np.eye(size + 1)[[*ornt[:, 0].astype(int), size], :]
+    undo_flip = np.diag([*ornt[:, 1], 1.0])
+    centre = -(extent - 1) / 2.0
+    undo_flip[:size, size] = ornt[:, 1] * centre - centre
+    return undo_flip @ undo_reorder

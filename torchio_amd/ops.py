@@ -1483,6 +1483,31 @@ class Engine:
                    _i32x3(data.shape[2:]), mask, _ptr(flags), self._stream(data))
         return out
 
+    def permute3d(self, data: Tensor, perm: Sequence[int], flip_axes: Sequence[int] = ()) -> Tensor:
+        """``torch.flip(data, flip_axes)`` (spatial input axes 0..2), then ``permute(0, 1, 2 + perm[0], 2 + perm[1],
+        2 + perm[2]).contiguous()``, as one launch (``tio_permute3d``: nibabel's ``apply_orientation`` order)."""
+        if data.ndim != 5:
+            raise ValueError(f"expected a (B, C, I, J, K) tensor, got {tuple(data.shape)}")
+        perm = [int(p) for p in perm]
+        if sorted(perm) != [0, 1, 2]:
+            raise ValueError(f"perm must be a permutation of (0, 1, 2), got {tuple(perm)}")
+        mask = 0
+        for axis in flip_axes:
+            if axis not in (0, 1, 2):
+                raise ValueError(f"Axis must be 0, 1, or 2; got {axis}")
+            mask |= 1 << int(axis)
+        if _wants_grad(data):  # the transpose of a permutation is its inverse: the flips move to the axes they land on
+            result = self.permute3d(data.detach(), perm, flip_axes)
+            inverse = [perm.index(d) for d in range(3)]
+            carried = [d for d in range(3) if mask & (1 << perm[d])]
+            return _AttachBackward.apply(data, result, lambda grad: self.permute3d(grad, inverse, carried))
+        data = data.contiguous()
+        self._check("permute3d", data)
+        out = torch.empty((*data.shape[:2], *(data.shape[2 + p] for p in perm)), dtype=data.dtype, device=data.device)
+        self._call("permute3d", data, _ptr(data), _ptr(out), dtype_code(data.dtype), data.shape[0], data.shape[1],
+                   _i32x3(data.shape[2:]), _i32x3(perm), mask, self._stream(data))
+        return out
+
     def pad3d(self, data: Tensor, padding: Sequence[int], mode: str = "constant", fill: float = 0.0,
               fill_per_element: Tensor | None = None) -> Tensor:
         """``F.pad`` of the three spatial axes: ``padding = (i0, i1, j0, j1, k0, k1)``, ``mode`` as in ``F.pad``.

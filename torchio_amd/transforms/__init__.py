@@ -27,6 +27,12 @@ from .normalize import Normalize
 from .normalize import RescaleIntensity
 from .normalize import Standardize
 from .normalize import ZNormalization
+from .orientation import CopyAffine
+from .orientation import CropOrPad
+from .orientation import EnsureShapeMultiple
+from .orientation import Reorient
+from .orientation import ToReferenceSpace
+from .orientation import Transpose
 from .pad import Crop
 from .pad import Pad
 from .parameter_range import Choice
@@ -43,8 +49,8 @@ from .transform import SpatialTransform
 from .transform import Transform
 
 __all__ = [
-    "Affine", "Anisotropy", "AppliedTransform", "BiasField", "Blur", "Choice", "Clamp", "Compose", "Contour", "Crop", "ElasticDeformation", "Flip", "Gamma", "Ghosting",
-    "HistogramStandardization", "IntensityTransform", "KeepLargestComponent", "LabelsToImage", "Mask", "Motion", "Noise", "Normalize", "OneHot", "OneOf", "Pad", "RemapLabels", "RemoveLabels", "Resample", "RescaleIntensity",
-    "Resize", "SequentialLabels", "SomeOf", "Spatial", "SpatialTransform", "Spike", "Standardize", "Swap", "Transform", "ZNormalization",
+    "Affine", "Anisotropy", "AppliedTransform", "BiasField", "Blur", "Choice", "Clamp", "Compose", "Contour", "CopyAffine", "Crop", "CropOrPad", "ElasticDeformation", "EnsureShapeMultiple", "Flip", "Gamma", "Ghosting",
+    "HistogramStandardization", "IntensityTransform", "KeepLargestComponent", "LabelsToImage", "Mask", "Motion", "Noise", "Normalize", "OneHot", "OneOf", "Pad", "RemapLabels", "RemoveLabels", "Reorient", "Resample", "RescaleIntensity",
+    "Resize", "SequentialLabels", "SomeOf", "Spatial", "SpatialTransform", "Spike", "Standardize", "Swap", "ToReferenceSpace", "Transform", "Transpose", "ZNormalization",
     "apply_inverse_transform", "get_inverse_transform", "get_noise_rng", "set_noise_rng",
 ]
