@@ -56,6 +56,104 @@ def test_argument_validation_without_a_gpu():
     assert functions["add_noise"](None, None, 0, 1, 1, 0.0, 1.0, None, None, 0, 0, None, None, 0, None, None) == -1
 
 
+def _calls_valid_in_everything_but_the_dtype(functions):
+    """name -> call(dtype) for every entry point that takes a ``tio_dtype``; a second entry per mask dtype.
+
+    Batch 1, one channel, a (4, 4, 4) volume, radius (1, 1, 1); every pointer is a host buffer nobody dereferences.
+    """
+    buffers = [ctypes.create_string_buffer(4096 + 16) for _ in range(8)]
+    p = [ctypes.c_void_p((ctypes.addressof(b) + 15) & ~15) for b in buffers]  # 16-byte aligned, pairwise disjoint
+    x, y, tmp, aux = p[0], p[1], p[2], p[3:]
+    n = 64
+    i32x3 = ctypes.c_int32 * 3
+    shape, radius, coarse = i32x3(4, 4, 4), i32x3(1, 1, 1), i32x3(2, 2, 2)
+    ws_bytes = max(
+        functions["intensity_stats_workspace_bytes"](),
+        functions["intensity_multi_quantiles_workspace_bytes"](1, 1),
+        functions["keep_largest_workspace_bytes"](1, shape, 1),
+    )
+    half = (ctypes.c_double * 1)(0.5)
+    passes = (_abi.ConvPass * 3)()
+    placement = (_abi.PatchPlacement * 1)()
+    placement[0].extent[:] = [4, 4, 4]
+    segments = (ctypes.c_void_p * 1)(x)
+    geom = _abi.ResampleGeom()
+    geom.batch = 1
+    geom.in_shape[:] = geom.out_shape[:] = [4, 4, 4]
+    geom.in_spacing[:] = geom.out_spacing[:] = [1.0, 1.0, 1.0]
+    geom.mapping_dev = aux[0]
+
+    def resample(dtype):
+        image = (_abi.ResampleImage * 1)()
+        image[0].in_, image[0].out, image[0].channels, image[0].dtype, image[0].interp = x, y, 1, dtype, _abi.LINEAR
+        return functions["resample3d"](ctypes.byref(geom), 1, image, None)
+
+    f = functions
+    calls = {
+        "resample3d": resample,
+        "channel_min": lambda d: f["channel_min"](x, d, 1, n, y, None),
+        "separable_conv3d": lambda d: f["separable_conv3d"](x, y, tmp, d, 1, 1, shape, aux[0], 0, 3, radius, None, None),
+        "separable_conv3d_passes": lambda d: f["separable_conv3d_passes"](d, 1, 1, shape, radius, 1, 0, 0, 0, 0, passes),
+        "bias_field_apply": lambda d: f["bias_field_apply"](x, y, d, 1, 1, shape, aux[0], coarse, 0, None, None),
+        "add_noise": lambda d: f["add_noise"](x, y, d, 1, n, 0.0, 1.0, None, None, 0, 0, None, None, 0, None, None),
+        "gamma_pow": lambda d: f["gamma_pow"](x, y, d, 1, n, 1.5, None, 0, None),
+        "patch_accumulate": lambda d: f["patch_accumulate"](y, None, d, 1, shape, x, 1, shape, placement, _abi.OVERLAP_CROP, None, None, None, None),
+        "bspline_prefilter": lambda d: f["bspline_prefilter"](x, y, d, 1, shape, 3, None),
+        "interpolate3d": lambda d: f["interpolate3d"](x, y, d, 1, shape, shape, _abi.LINEAR, None),
+        "axis_gather_lerp": lambda d: f["axis_gather_lerp"](x, y, d, 1, 1, shape, 0, aux[0], None, None, None, None),
+        "flip3d": lambda d: f["flip3d"](x, y, d, 1, 1, shape, 1, None, None),
+        "pad3d": lambda d: f["pad3d"](x, y, d, 1, 1, shape, (ctypes.c_int32 * 6)(1, 1, 1, 1, 1, 1), _abi.PAD_CONSTANT, 0.0, None, None),
+        "permute3d": lambda d: f["permute3d"](x, y, d, 1, 1, shape, i32x3(2, 1, 0), 0, None),
+        "unique_labels": lambda d: f["unique_labels"](x, d, n, aux[0], aux[1], aux[2], None),
+        "kspace_segment_mix": lambda d: f["kspace_segment_mix"](segments, 1, (ctypes.c_int32 * 2)(0, 4), aux[0], y, d, 1, 1, shape, None, None),
+        "label_remap": lambda d: f["label_remap"](x, y, d, n, aux[0], aux[1], 1, _abi.REMAP_KEEP, 0.0, aux[2], None),
+        "label_one_hot": lambda d: f["label_one_hot"](x, y, d, 1, n, 2, aux[0], None),
+        "label_contour": lambda d: f["label_contour"](x, y, d, 1, shape, None),
+        "keep_largest_component": lambda d: f["keep_largest_component"](x, y, d, 1, shape, aux[0], 1, 0.0, 0, aux[1], ws_bytes, None),
+        "intensity_moments": lambda d: f["intensity_moments"](x, d, 1, n, None, 0, 1, aux[0], aux[1], ws_bytes, None),
+        "intensity_moments (mask)": lambda d: f["intensity_moments"](x, _abi.F32, 1, n, y, d, 1, aux[0], aux[1], ws_bytes, None),
+        "intensity_quantiles": lambda d: f["intensity_quantiles"](x, d, 1, n, None, 0, 1, half, 1, aux[0], aux[1], ws_bytes, None),
+        "intensity_quantiles (mask)": lambda d: f["intensity_quantiles"](x, _abi.F32, 1, n, y, d, 1, half, 1, aux[0], aux[1], ws_bytes, None),
+        "intensity_map": lambda d: f["intensity_map"](x, y, d, 1, n, _abi.MAP_RESCALE, 0.0, 1.0, 1.0, 0.0, 1.0, None, None, None),
+        "intensity_clamp": lambda d: f["intensity_clamp"](x, y, d, n, 1, 0.0, 1, 1.0, None),
+        "intensity_mask": lambda d: f["intensity_mask"](x, y, d, n, tmp, _abi.U8, n, 0.0, None),
+        "intensity_mask (mask)": lambda d: f["intensity_mask"](x, y, _abi.F32, n, tmp, d, n, 0.0, None),
+        "intensity_multi_quantiles": lambda d: f["intensity_multi_quantiles"](x, d, 1, 1, n, None, 0, 1, half, 1, aux[0], aux[1], aux[2], ws_bytes, None),
+        "intensity_multi_quantiles (mask)": lambda d: f["intensity_multi_quantiles"](
+            x, _abi.F32, 1, 1, n, y, d, 1, half, 1, aux[0], aux[1], aux[2], ws_bytes, None
+        ),
+        "histogram_standardize": lambda d: f["histogram_standardize"](x, y, d, 1, n, aux[0], aux[1], 2, aux[2], None),
+        "kspace_ghost_lines": lambda d: f["kspace_ghost_lines"](x, y, d, 1, 1, shape, 1, aux[0], 4, 0, aux[1], None, None),
+        "kspace_add_spikes": lambda d: f["kspace_add_spikes"](x, y, d, 1, 1, shape, aux[0], 4, 0, aux[1], aux[2], None, None),
+        "labels_to_image": lambda d: f["labels_to_image"](x, d, 1, 1, n, aux[0], 1, aux[1], aux[2], 0, y, 0, None, 0, None),
+    }
+    fused = lambda d: f["blur_fused"](  # noqa: E731
+        x, y, tmp, d, 1, 1, shape, aux[0], 0, 3, radius, None, None, 0, 0.0, 1.0, None, None, 0, 0, None, 0, None
+    )
+    return calls, fused, (buffers, segments, geom)
+
+
+def test_unknown_dtype_codes_are_refused_by_every_entry_point_without_a_gpu():
+    """A code outside the nine of ``tio_dtype`` is TIO_ERR_UNSUPPORTED_DTYPE everywhere, and the message names the entry point.
+
+    The calls are valid in everything else, so the answer comes from the dtype check (or, were that ever dropped, from the
+    dispatch behind it): no kernel is launched, no buffer is read.  ``tio_blur_fused`` runs float32 only and answers every
+    other code, known or not, with TIO_ERR_UNSUPPORTED_CONFIG ("take the unfused calls") and leaves the error text alone.
+    """
+    _, functions = _lib.load()
+    calls, fused, keep_alive = _calls_valid_in_everything_but_the_dtype(functions)
+    # every declaration of the header with a dtype parameter is probed (tio_resample3d takes its dtypes in tio_resample_image)
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    declared = {name for name, args in re.findall(r"\btio_([a-z0-9_]+)\s*\(([^;{}]*)\)\s*;", text) if "dtype" in args}
+    assert declared | {"resample3d"} == {name.split(" ")[0] for name in calls} | {"blur_fused"}
+    for dtype in (9, -1, 1000):
+        for name, call in calls.items():
+            assert call(dtype) == -2, (name, dtype, functions["last_error"]())
+            assert b"tio_" + name.split(" ")[0].encode() in functions["last_error"](), (name, dtype, functions["last_error"]())
+        assert fused(dtype) == _abi.UNSUPPORTED_CONFIG
+    del keep_alive
+
+
 def test_kspace_mix_table_direct_sum_equals_the_closed_form_and_is_a_partition_of_unity():
     """Host helper of the HIP library (no GPU): W_s summed directly vs the oracle's Dirichlet-kernel form."""
     import numpy as np

@@ -158,7 +158,7 @@ extern "C" int tio_patch_accumulate(void* out, void* weight_sum, int32_t dtype, 
   if (channels < 1 || n_patches < 0 || n_patches > TIO_MAX_PATCHES)
     return fail(TIO_ERR_INVALID_ARGUMENT, "tio_patch_accumulate: channels=%d n_patches=%d (max %d)", channels, n_patches,
                 TIO_MAX_PATCHES);
-  if (dtype_size(dtype) == 0) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_patch_accumulate: dtype %d", dtype);
+  if (!is_known_dtype(dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_patch_accumulate: dtype %d", dtype);
   if (mode != TIO_OVERLAP_CROP) {
     if (!is_float_dtype(dtype))
       return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_patch_accumulate: 'average' / 'hann' need a floating dtype, got %d", dtype);
@@ -196,15 +196,7 @@ extern "C" int tio_patch_accumulate(void* out, void* weight_sum, int32_t dtype, 
     a.box_ext[d] = hi[d] - lo[d];
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (dtype) {
-    case TIO_F32: return launch_accumulate<TIO_F32>(a, s);
-    case TIO_F64: return launch_accumulate<TIO_F64>(a, s);
-    case TIO_F16: return launch_accumulate<TIO_F16>(a, s);
-    case TIO_BF16: return launch_accumulate<TIO_BF16>(a, s);
-    case TIO_U8: return launch_accumulate<TIO_U8>(a, s);
-    case TIO_I8: return launch_accumulate<TIO_I8>(a, s);
-    case TIO_I16: return launch_accumulate<TIO_I16>(a, s);
-    case TIO_I32: return launch_accumulate<TIO_I32>(a, s);
-    default: return launch_accumulate<TIO_I64>(a, s);
-  }
+  int status = TIO_OK;
+  const bool known = dispatch_dtype(dtype, [&](auto dt) { status = launch_accumulate<decltype(dt)::value>(a, s); });
+  return known ? status : fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_patch_accumulate: dtype %d", dtype);
 }

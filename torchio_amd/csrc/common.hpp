@@ -159,6 +159,65 @@ inline bool is_float_dtype(int dtype) {
   return dtype == TIO_F32 || dtype == TIO_F64 || dtype == TIO_F16 || dtype == TIO_BF16;
 }
 
+inline bool is_known_dtype(int dtype) { return dtype_size(dtype) != 0; }
+
+// ---- host-side dispatch: a run-time code becomes a compile-time constant --------
+// The one place on the host that lists the dtype codes.  Each entry calls `f` with a tag whose `value` is a constant
+// expression (`kernel<decltype(tag)::value>`), and returns false, having called nothing, for a code it does not list.
+template <int DT>
+struct DtypeTag {
+  static constexpr int value = DT;
+};
+template <int ES>
+struct SizeTag {
+  static constexpr int value = ES;
+};
+
+template <typename F>
+[[nodiscard]] inline bool dispatch_float_dtype(int dtype, F&& f) {
+  switch (dtype) {
+    case TIO_F32: f(DtypeTag<TIO_F32>{}); return true;
+    case TIO_F64: f(DtypeTag<TIO_F64>{}); return true;
+    case TIO_F16: f(DtypeTag<TIO_F16>{}); return true;
+    case TIO_BF16: f(DtypeTag<TIO_BF16>{}); return true;
+    default: return false;
+  }
+}
+
+template <typename F>
+[[nodiscard]] inline bool dispatch_dtype(int dtype, F&& f) {
+  switch (dtype) {
+    case TIO_F32: f(DtypeTag<TIO_F32>{}); return true;
+    case TIO_F64: f(DtypeTag<TIO_F64>{}); return true;
+    case TIO_F16: f(DtypeTag<TIO_F16>{}); return true;
+    case TIO_BF16: f(DtypeTag<TIO_BF16>{}); return true;
+    case TIO_U8: f(DtypeTag<TIO_U8>{}); return true;
+    case TIO_I8: f(DtypeTag<TIO_I8>{}); return true;
+    case TIO_I16: f(DtypeTag<TIO_I16>{}); return true;
+    case TIO_I32: f(DtypeTag<TIO_I32>{}); return true;
+    case TIO_I64: f(DtypeTag<TIO_I64>{}); return true;
+    default: return false;
+  }
+}
+
+template <typename F>
+[[nodiscard]] inline bool dispatch_element_size(int element_size, F&& f) {
+  switch (element_size) {
+    case 1: f(SizeTag<1>{}); return true;
+    case 2: f(SizeTag<2>{}); return true;
+    case 4: f(SizeTag<4>{}); return true;
+    case 8: f(SizeTag<8>{}); return true;
+    default: return false;
+  }
+}
+
+// The unsigned integer of ES bytes: what a kernel that only moves elements loads and stores.
+template <int ES> struct RawBits;
+template <> struct RawBits<1> { typedef uint8_t type; };
+template <> struct RawBits<2> { typedef uint16_t type; };
+template <> struct RawBits<4> { typedef uint32_t type; };
+template <> struct RawBits<8> { typedef uint64_t type; };
+
 // ---- ATen upsample_linear (align_corners=True) source index / lambdas ---------
 struct Lerp1D {
   int i0, i1;

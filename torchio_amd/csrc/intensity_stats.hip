@@ -15,6 +15,8 @@
 #include <math.h>
 #include <string.h>
 
+#include <type_traits>
+
 namespace tio {
 namespace {
 
@@ -505,7 +507,9 @@ __global__ __launch_bounds__(256) void mask_kernel(const typename Elem<DT>::type
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-bool known_dtype(int dtype) { return dtype >= 0 && dtype <= TIO_I64 && dtype_size(dtype) != 0; }
+// the pass number of a selection kernel, handed to a generic lambda as a compile-time constant
+template <int N>
+using Pass = std::integral_constant<int, N>;
 
 // a Python float as the dtype's scalar (c10::Scalar::to<T>: through float32 for the 16-bit floats), back as a double
 double scalar_in_dtype(double v, int dtype) {
@@ -525,8 +529,8 @@ double scalar_in_dtype(double v, int dtype) {
 // the checks the two statistics share; *n is channels * n_spatial
 int check_stats_arguments(const char* who, const void* x, int dtype, int channels, int64_t n_spatial, const void* mask, int mask_dtype,
                           int mask_channels, const void* record, const void* workspace, int64_t workspace_bytes, MaskView* view, int64_t* n) {
-  if (!known_dtype(dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "%s: unknown dtype %d", who, dtype);
-  if (mask != nullptr && !known_dtype(mask_dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "%s: unknown mask dtype %d", who, mask_dtype);
+  if (!is_known_dtype(dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "%s: unknown dtype %d", who, dtype);
+  if (mask != nullptr && !is_known_dtype(mask_dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "%s: unknown mask dtype %d", who, mask_dtype);
   if (channels < 0 || n_spatial < 0) return fail(TIO_ERR_INVALID_ARGUMENT, "%s: negative size", who);
   if (mask != nullptr && mask_channels != 1 && mask_channels != channels)
     return fail(TIO_ERR_INVALID_ARGUMENT, "%s: %d mask channels for %d data channels (1 or as many)", who, mask_channels, channels);
@@ -834,19 +838,6 @@ __global__ __launch_bounds__(256) void standardize_apply_kernel(const typename E
 }  // namespace
 }  // namespace tio
 
-#define TIO_FOR_EACH_DTYPE(dtype, CASE) \
-  switch (dtype) {                      \
-    case TIO_F32: CASE(TIO_F32); break; \
-    case TIO_F64: CASE(TIO_F64); break; \
-    case TIO_F16: CASE(TIO_F16); break; \
-    case TIO_BF16: CASE(TIO_BF16); break; \
-    case TIO_U8: CASE(TIO_U8); break;   \
-    case TIO_I8: CASE(TIO_I8); break;   \
-    case TIO_I16: CASE(TIO_I16); break; \
-    case TIO_I32: CASE(TIO_I32); break; \
-    default: CASE(TIO_I64); break;      \
-  }
-
 extern "C" int64_t tio_intensity_stats_workspace_bytes(void) { return tio::kStatsWorkspaceBytes; }
 
 extern "C" int tio_intensity_moments(const void* x, int32_t dtype, int32_t channels, int64_t n_spatial, const void* mask, int32_t mask_dtype,
@@ -860,9 +851,10 @@ extern "C" int tio_intensity_moments(const void* x, int32_t dtype, int32_t chann
   hipStream_t s = static_cast<hipStream_t>(stream);
   Moments* partial = static_cast<Moments*>(workspace_dev);
   const unsigned blocks = reduce_blocks(n, kMomentBlocks);
-#define TIO_MOMENTS(DT) hipLaunchKernelGGL(moments_partial_kernel<DT>, dim3(blocks), dim3(256), 0, s, x, n, view, partial)
-  TIO_FOR_EACH_DTYPE(dtype, TIO_MOMENTS)
-#undef TIO_MOMENTS
+  const bool known = dispatch_dtype(dtype, [&](auto dt) {
+    hipLaunchKernelGGL(moments_partial_kernel<decltype(dt)::value>, dim3(blocks), dim3(256), 0, s, x, n, view, partial);
+  });
+  if (!known) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_intensity_moments: unknown dtype %d", dtype);
   if (const int rc = check_launch("tio_intensity_moments (partials)")) return rc;
   hipLaunchKernelGGL(moments_final_kernel, dim3(1), dim3(256), 0, s, partial, static_cast<int>(blocks), static_cast<MomentsRecord*>(record_dev));
   return check_launch("tio_intensity_moments");
@@ -890,23 +882,20 @@ extern "C" int tio_intensity_quantiles(const void* x, int32_t dtype, int32_t cha
   if (hipMemsetAsync(hist, 0, kSelectHistBytes, s) != hipSuccess) return fail(TIO_ERR_LAUNCH, "tio_intensity_quantiles: memset failed");
   const dim3 grid(reduce_blocks(n, kSelectBlocks)), block(256);
   const double q0 = fractions[0], q1 = n_fractions > 1 ? fractions[1] : fractions[0];
-#define TIO_SELECT_1(DT) hipLaunchKernelGGL((select_histogram_kernel<DT, 1>), grid, block, 0, s, x, n, view, state, hist)
-#define TIO_SELECT_2(DT) hipLaunchKernelGGL((select_histogram_kernel<DT, 2>), grid, block, 0, s, x, n, view, state, hist)
-#define TIO_SELECT_3(DT) hipLaunchKernelGGL((select_histogram_kernel<DT, 3>), grid, block, 0, s, x, n, view, state, hist)
-  TIO_FOR_EACH_DTYPE(dtype, TIO_SELECT_1)
-  if (const int rc = check_launch("tio_intensity_quantiles (pass 1)")) return rc;
+  const auto histogram = [&](auto pass, const char* what) {
+    const bool known = dispatch_dtype(dtype, [&](auto dt) {
+      hipLaunchKernelGGL((select_histogram_kernel<decltype(dt)::value, decltype(pass)::value>), grid, block, 0, s, x, n, view, state, hist);
+    });
+    return known ? check_launch(what) : fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_intensity_quantiles: unknown dtype %d", dtype);
+  };
+  if (const int rc = histogram(Pass<1>{}, "tio_intensity_quantiles (pass 1)")) return rc;
   hipLaunchKernelGGL(select_scan_kernel<1>, dim3(1), block, 0, s, state, hist, q0, q1, n_fractions, record);
   if (const int rc = check_launch("tio_intensity_quantiles (scan 1)")) return rc;
-  TIO_FOR_EACH_DTYPE(dtype, TIO_SELECT_2)
-  if (const int rc = check_launch("tio_intensity_quantiles (pass 2)")) return rc;
+  if (const int rc = histogram(Pass<2>{}, "tio_intensity_quantiles (pass 2)")) return rc;
   hipLaunchKernelGGL(select_scan_kernel<2>, dim3(1), block, 0, s, state, hist, q0, q1, n_fractions, record);
   if (const int rc = check_launch("tio_intensity_quantiles (scan 2)")) return rc;
-  TIO_FOR_EACH_DTYPE(dtype, TIO_SELECT_3)
-  if (const int rc = check_launch("tio_intensity_quantiles (pass 3)")) return rc;
+  if (const int rc = histogram(Pass<3>{}, "tio_intensity_quantiles (pass 3)")) return rc;
   hipLaunchKernelGGL(select_scan_kernel<3>, dim3(1), block, 0, s, state, hist, q0, q1, n_fractions, record);
-#undef TIO_SELECT_1
-#undef TIO_SELECT_2
-#undef TIO_SELECT_3
   return check_launch("tio_intensity_quantiles");
 }
 
@@ -914,7 +903,7 @@ extern "C" int tio_intensity_map(const void* x, float* y, int32_t dtype, int32_t
                                  float in_max, float in_range, float out_min, float out_range, const float* out_min_dev,
                                  const float* out_range_dev, void* stream) {
   using namespace tio;
-  if (!known_dtype(dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_intensity_map: unknown dtype %d", dtype);
+  if (!is_known_dtype(dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_intensity_map: unknown dtype %d", dtype);
   if (batch < 0 || n_per_element < 0) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_intensity_map: negative size");
   if (mode < TIO_MAP_RESCALE_CLIP || mode > TIO_MAP_MUL_ADD) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_intensity_map: unknown mode %d", mode);
   if ((out_min_dev == nullptr) != (out_range_dev == nullptr))
@@ -928,16 +917,17 @@ extern "C" int tio_intensity_map(const void* x, float* y, int32_t dtype, int32_t
   const MapParams p = {mode, in_min, in_max, in_range, out_min, out_range, out_min_dev, out_range_dev, n_per_element};
   hipStream_t s = static_cast<hipStream_t>(stream);
   const dim3 grid(stream_blocks(n)), block(256);
-#define TIO_MAP(DT) hipLaunchKernelGGL(map_kernel<DT>, grid, block, 0, s, static_cast<const Elem<DT>::type*>(x), y, n, p)
-  TIO_FOR_EACH_DTYPE(dtype, TIO_MAP)
-#undef TIO_MAP
-  return check_launch("tio_intensity_map");
+  const bool known = dispatch_dtype(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    hipLaunchKernelGGL(map_kernel<DT>, grid, block, 0, s, static_cast<const typename Elem<DT>::type*>(x), y, n, p);
+  });
+  return known ? check_launch("tio_intensity_map") : fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_intensity_map: unknown dtype %d", dtype);
 }
 
 extern "C" int tio_intensity_clamp(const void* x, void* y, int32_t dtype, int64_t n, int32_t has_min, double out_min, int32_t has_max,
                                    double out_max, void* stream) {
   using namespace tio;
-  if (!known_dtype(dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_intensity_clamp: unknown dtype %d", dtype);
+  if (!is_known_dtype(dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_intensity_clamp: unknown dtype %d", dtype);
   if (n < 0) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_intensity_clamp: negative size");
   if (!has_min && !has_max) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_intensity_clamp: at least one of the bounds");
   if ((has_min && out_min != out_min) || (has_max && out_max != out_max)) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_intensity_clamp: a bound is NaN");
@@ -946,18 +936,19 @@ extern "C" int tio_intensity_clamp(const void* x, void* y, int32_t dtype, int64_
   const double lo = scalar_in_dtype(out_min, dtype), hi = scalar_in_dtype(out_max, dtype);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const dim3 grid(stream_blocks(n)), block(256);
-#define TIO_CLAMP(DT) \
-  hipLaunchKernelGGL(clamp_kernel<DT>, grid, block, 0, s, static_cast<const Elem<DT>::type*>(x), static_cast<Promoted<DT>::Out*>(y), n, has_min, lo, has_max, hi)
-  TIO_FOR_EACH_DTYPE(dtype, TIO_CLAMP)
-#undef TIO_CLAMP
-  return check_launch("tio_intensity_clamp");
+  const bool known = dispatch_dtype(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    hipLaunchKernelGGL(clamp_kernel<DT>, grid, block, 0, s, static_cast<const typename Elem<DT>::type*>(x), static_cast<typename Promoted<DT>::Out*>(y), n,
+                       has_min, lo, has_max, hi);
+  });
+  return known ? check_launch("tio_intensity_clamp") : fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_intensity_clamp: unknown dtype %d", dtype);
 }
 
 extern "C" int tio_intensity_mask(const void* x, void* y, int32_t dtype, int64_t n, const void* mask, int32_t mask_dtype, int64_t mask_n,
                                   double outside_value, void* stream) {
   using namespace tio;
-  if (!known_dtype(dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_intensity_mask: unknown dtype %d", dtype);
-  if (!known_dtype(mask_dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_intensity_mask: unknown mask dtype %d", mask_dtype);
+  if (!is_known_dtype(dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_intensity_mask: unknown dtype %d", dtype);
+  if (!is_known_dtype(mask_dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_intensity_mask: unknown mask dtype %d", mask_dtype);
   if (n < 0 || mask_n < 0) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_intensity_mask: negative size");
   if (n == 0) return TIO_OK;
   if (mask_n == 0 || n % mask_n != 0)
@@ -965,14 +956,15 @@ extern "C" int tio_intensity_mask(const void* x, void* y, int32_t dtype, int64_t
                 static_cast<long long>(mask_n));
   if (x == nullptr || y == nullptr || mask == nullptr) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_intensity_mask: null argument");
   const MaskView view = {mask, dtype_size(mask_dtype), is_float_dtype(mask_dtype) ? 1 : 0, mask_n};
-  const double outside = scalar_in_dtype(outside_value, dtype_size(dtype) != 0 && is_float_dtype(dtype) ? dtype : TIO_F32);
+  const double outside = scalar_in_dtype(outside_value, is_float_dtype(dtype) ? dtype : TIO_F32);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const dim3 grid(stream_blocks(n)), block(256);
-#define TIO_MASK(DT) \
-  hipLaunchKernelGGL(mask_kernel<DT>, grid, block, 0, s, static_cast<const Elem<DT>::type*>(x), static_cast<Promoted<DT>::Out*>(y), n, view, outside)
-  TIO_FOR_EACH_DTYPE(dtype, TIO_MASK)
-#undef TIO_MASK
-  return check_launch("tio_intensity_mask");
+  const bool known = dispatch_dtype(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    hipLaunchKernelGGL(mask_kernel<DT>, grid, block, 0, s, static_cast<const typename Elem<DT>::type*>(x), static_cast<typename Promoted<DT>::Out*>(y), n, view,
+                       outside);
+  });
+  return known ? check_launch("tio_intensity_mask") : fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_intensity_mask: unknown dtype %d", dtype);
 }
 
 extern "C" int64_t tio_intensity_multi_quantiles_workspace_bytes(int32_t batch, int32_t n_fractions) {
@@ -1016,33 +1008,28 @@ extern "C" int tio_intensity_multi_quantiles(const void* x, int32_t dtype, int32
     return fail(TIO_ERR_LAUNCH, "%s: memset failed", who);
   const dim3 grid(reduce_blocks(n, kSelectBlocks), batch), block(256), one(batch);
   const size_t group_lds = static_cast<size_t>(ranks_cap) * kMultiBins * sizeof(unsigned);  // at most 33 280 bytes
-#define TIO_MULTI(DT, PASS, LDS) hipLaunchKernelGGL((multi_histogram_kernel<DT, PASS>), grid, block, LDS, s, x, n, view, states, hist1, hist_groups, ranks_cap)
-#define TIO_MULTI_1(DT) TIO_MULTI(DT, 1, 0)
-#define TIO_MULTI_2(DT) TIO_MULTI(DT, 2, group_lds)
-#define TIO_MULTI_3(DT) TIO_MULTI(DT, 3, group_lds)
-#define TIO_MULTI_4(DT) TIO_MULTI(DT, 4, group_lds)
-#define TIO_MULTI_SCAN(PASS) hipLaunchKernelGGL(multi_scan_kernel<PASS>, one, block, 0, s, states, hist1, hist_groups, ranks_cap, q, n_fractions, values_dev, counts_dev)
-  TIO_FOR_EACH_DTYPE(dtype, TIO_MULTI_1)
-  if (const int rc = check_launch("tio_intensity_multi_quantiles (pass 1)")) return rc;
-  TIO_MULTI_SCAN(1);
+  const auto histogram = [&](auto pass, const char* what) {
+    constexpr int PASS = decltype(pass)::value;
+    const bool known = dispatch_dtype(dtype, [&](auto dt) {
+      hipLaunchKernelGGL((multi_histogram_kernel<decltype(dt)::value, PASS>), grid, block, PASS == 1 ? 0 : group_lds, s, x, n, view, states, hist1,
+                         hist_groups, ranks_cap);
+    });
+    return known ? check_launch(what) : fail(TIO_ERR_UNSUPPORTED_DTYPE, "%s: unknown dtype %d", who, dtype);
+  };
+  const auto scan = [&](auto pass) {
+    hipLaunchKernelGGL(multi_scan_kernel<decltype(pass)::value>, one, block, 0, s, states, hist1, hist_groups, ranks_cap, q, n_fractions, values_dev, counts_dev);
+  };
+  if (const int rc = histogram(Pass<1>{}, "tio_intensity_multi_quantiles (pass 1)")) return rc;
+  scan(Pass<1>{});
   if (const int rc = check_launch("tio_intensity_multi_quantiles (scan 1)")) return rc;
-  TIO_FOR_EACH_DTYPE(dtype, TIO_MULTI_2)
-  if (const int rc = check_launch("tio_intensity_multi_quantiles (pass 2)")) return rc;
-  TIO_MULTI_SCAN(2);
+  if (const int rc = histogram(Pass<2>{}, "tio_intensity_multi_quantiles (pass 2)")) return rc;
+  scan(Pass<2>{});
   if (const int rc = check_launch("tio_intensity_multi_quantiles (scan 2)")) return rc;
-  TIO_FOR_EACH_DTYPE(dtype, TIO_MULTI_3)
-  if (const int rc = check_launch("tio_intensity_multi_quantiles (pass 3)")) return rc;
-  TIO_MULTI_SCAN(3);
+  if (const int rc = histogram(Pass<3>{}, "tio_intensity_multi_quantiles (pass 3)")) return rc;
+  scan(Pass<3>{});
   if (const int rc = check_launch("tio_intensity_multi_quantiles (scan 3)")) return rc;
-  TIO_FOR_EACH_DTYPE(dtype, TIO_MULTI_4)
-  if (const int rc = check_launch("tio_intensity_multi_quantiles (pass 4)")) return rc;
-  TIO_MULTI_SCAN(4);
-#undef TIO_MULTI
-#undef TIO_MULTI_1
-#undef TIO_MULTI_2
-#undef TIO_MULTI_3
-#undef TIO_MULTI_4
-#undef TIO_MULTI_SCAN
+  if (const int rc = histogram(Pass<4>{}, "tio_intensity_multi_quantiles (pass 4)")) return rc;
+  scan(Pass<4>{});
   return check_launch(who);
 }
 
@@ -1050,7 +1037,7 @@ extern "C" int tio_histogram_standardize(const void* x, void* y, int32_t dtype, 
                                          const float* landmarks_dev, int32_t n_landmarks, float* table_dev, void* stream) {
   using namespace tio;
   const char* who = "tio_histogram_standardize";
-  if (!known_dtype(dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "%s: unknown dtype %d", who, dtype);
+  if (!is_known_dtype(dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "%s: unknown dtype %d", who, dtype);
   if (batch < 0 || n_per_element < 0) return fail(TIO_ERR_INVALID_ARGUMENT, "%s: negative size", who);
   if (n_landmarks < 2 || n_landmarks > kMaxLandmarks) return fail(TIO_ERR_INVALID_ARGUMENT, "%s: 2 to %d landmarks, got %d", who, kMaxLandmarks, n_landmarks);
   if (batch > 0 && n_per_element > (int64_t{1} << 40) / batch) return fail(TIO_ERR_UNSUPPORTED_CONFIG, "%s: more than 2^40 elements", who);
@@ -1062,9 +1049,10 @@ extern "C" int tio_histogram_standardize(const void* x, void* y, int32_t dtype, 
   hipLaunchKernelGGL(standardize_table_kernel, dim3(1), dim3(256), 0, s, percentiles_dev, landmarks_dev, n_landmarks, batch, table_dev);
   if (const int rc = check_launch("tio_histogram_standardize (table)")) return rc;
   const dim3 grid(stream_blocks(n_per_element), batch), block(256);
-#define TIO_STANDARDIZE(DT) \
-  hipLaunchKernelGGL(standardize_apply_kernel<DT>, grid, block, 0, s, static_cast<const Elem<DT>::type*>(x), static_cast<Elem<DT>::type*>(y), n_per_element, table_dev, n_landmarks)
-  TIO_FOR_EACH_DTYPE(dtype, TIO_STANDARDIZE)
-#undef TIO_STANDARDIZE
-  return check_launch(who);
+  const bool known = dispatch_dtype(dtype, [&](auto dt) {
+    using T = typename Elem<decltype(dt)::value>::type;
+    hipLaunchKernelGGL(standardize_apply_kernel<decltype(dt)::value>, grid, block, 0, s, static_cast<const T*>(x), static_cast<T*>(y), n_per_element, table_dev,
+                       n_landmarks);
+  });
+  return known ? check_launch(who) : fail(TIO_ERR_UNSUPPORTED_DTYPE, "%s: unknown dtype %d", who, dtype);
 }

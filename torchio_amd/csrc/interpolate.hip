@@ -137,8 +137,7 @@ struct FlipArgs {
 
 template <int ES>
 __global__ __launch_bounds__(256) void flip_kernel(const FlipArgs a) {
-  using RAW = typename std::conditional<ES == 1, uint8_t, typename std::conditional<ES == 2, uint16_t,
-              typename std::conditional<ES == 4, uint32_t, uint64_t>::type>::type>::type;
+  using RAW = typename RawBits<ES>::type;
   const int64_t n = static_cast<int64_t>(a.shape[0]) * a.shape[1] * a.shape[2];
   const int64_t total = n * a.batch * a.channels;
   for (int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; t < total;
@@ -183,8 +182,7 @@ __device__ __forceinline__ int pad_source(int q, int n, int mode) {
 
 template <int ES>
 __global__ __launch_bounds__(256) void pad_kernel(const PadArgs a) {
-  using RAW = typename std::conditional<ES == 1, uint8_t, typename std::conditional<ES == 2, uint16_t,
-              typename std::conditional<ES == 4, uint32_t, uint64_t>::type>::type>::type;
+  using RAW = typename RawBits<ES>::type;
   const int64_t n_out = static_cast<int64_t>(a.out[0]) * a.out[1] * a.out[2];
   const int64_t n_in = static_cast<int64_t>(a.in[0]) * a.in[1] * a.in[2];
   const int64_t total = n_out * a.batch * a.channels;
@@ -223,25 +221,12 @@ static int launch_stream(Kernel kernel, const Args& a, int64_t total, hipStream_
 
 }  // namespace tio
 
-#define TIO_DISPATCH_DTYPE(DTYPE, CALL) \
-  switch (DTYPE) {                      \
-    case TIO_F32: CALL(TIO_F32); break; \
-    case TIO_F64: CALL(TIO_F64); break; \
-    case TIO_F16: CALL(TIO_F16); break; \
-    case TIO_BF16: CALL(TIO_BF16); break; \
-    case TIO_U8: CALL(TIO_U8); break;   \
-    case TIO_I8: CALL(TIO_I8); break;   \
-    case TIO_I16: CALL(TIO_I16); break; \
-    case TIO_I32: CALL(TIO_I32); break; \
-    default: CALL(TIO_I64); break;      \
-  }
-
 extern "C" int tio_interpolate3d(const void* x, void* y, int32_t dtype, int64_t n_batch_channels, const int32_t in_shape[3],
                                  const int32_t out_shape[3], int32_t mode, void* stream) {
   using namespace tio;
   if (in_shape == nullptr || out_shape == nullptr) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_interpolate3d: null shape");
   if (mode != TIO_NEAREST && mode != TIO_LINEAR) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_interpolate3d: mode %d", mode);
-  if (dtype_size(dtype) == 0) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_interpolate3d: dtype %d", dtype);
+  if (!is_known_dtype(dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_interpolate3d: dtype %d", dtype);
   if (n_batch_channels < 0) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_interpolate3d: negative batch");
   InterpArgs a{};
   a.x = x; a.y = y; a.n_bc = n_batch_channels; a.mode = mode;
@@ -256,10 +241,9 @@ extern "C" int tio_interpolate3d(const void* x, void* y, int32_t dtype, int64_t 
   if (x == nullptr || y == nullptr) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_interpolate3d: null data");
   const int64_t total = static_cast<int64_t>(out_shape[0]) * out_shape[1] * out_shape[2] * n_batch_channels;
   hipStream_t s = static_cast<hipStream_t>(stream);
-#define TIO_CALL(DT) return launch_stream(interpolate_kernel<DT>, a, total, s, "tio_interpolate3d")
-  TIO_DISPATCH_DTYPE(dtype, TIO_CALL)
-#undef TIO_CALL
-  return TIO_OK;
+  int status = TIO_OK;
+  const bool known = dispatch_dtype(dtype, [&](auto dt) { status = launch_stream(interpolate_kernel<decltype(dt)::value>, a, total, s, "tio_interpolate3d"); });
+  return known ? status : fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_interpolate3d: dtype %d", dtype);
 }
 
 extern "C" int tio_axis_gather_lerp(const void* x, void* y, int32_t dtype, int32_t batch, int32_t channels, const int32_t shape[3],
@@ -268,7 +252,7 @@ extern "C" int tio_axis_gather_lerp(const void* x, void* y, int32_t dtype, int32
   using namespace tio;
   if (shape == nullptr) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_axis_gather_lerp: null shape");
   if (axis < 0 || axis > 2) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_axis_gather_lerp: axis %d", axis);
-  if (dtype_size(dtype) == 0) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_axis_gather_lerp: dtype %d", dtype);
+  if (!is_known_dtype(dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_axis_gather_lerp: dtype %d", dtype);
   if (batch < 0 || channels < 1) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_axis_gather_lerp: bad batch / channels");
   if (batch == 0) return TIO_OK;
   if (x == nullptr || y == nullptr || lower_dev == nullptr) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_axis_gather_lerp: null argument");
@@ -282,10 +266,9 @@ extern "C" int tio_axis_gather_lerp(const void* x, void* y, int32_t dtype, int32
   }
   const int64_t total = static_cast<int64_t>(shape[0]) * shape[1] * shape[2] * batch * channels;
   hipStream_t s = static_cast<hipStream_t>(stream);
-#define TIO_CALL(DT) return launch_stream(axis_gather_lerp_kernel<DT>, a, total, s, "tio_axis_gather_lerp")
-  TIO_DISPATCH_DTYPE(dtype, TIO_CALL)
-#undef TIO_CALL
-  return TIO_OK;
+  int status = TIO_OK;
+  const bool known = dispatch_dtype(dtype, [&](auto dt) { status = launch_stream(axis_gather_lerp_kernel<decltype(dt)::value>, a, total, s, "tio_axis_gather_lerp"); });
+  return known ? status : fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_axis_gather_lerp: dtype %d", dtype);
 }
 
 extern "C" int tio_flip3d(const void* x, void* y, int32_t dtype, int32_t batch, int32_t channels, const int32_t shape[3],
@@ -293,7 +276,7 @@ extern "C" int tio_flip3d(const void* x, void* y, int32_t dtype, int32_t batch, 
   using namespace tio;
   if (shape == nullptr) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_flip3d: null shape");
   const int es = dtype_size(dtype);
-  if (es == 0) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_flip3d: dtype %d", dtype);
+  if (!is_known_dtype(dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_flip3d: dtype %d", dtype);
   if (batch < 0 || channels < 1 || axes_mask < 0 || axes_mask > 7) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_flip3d: bad argument");
   if (batch == 0) return TIO_OK;
   if (x == nullptr || y == nullptr) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_flip3d: null data");
@@ -305,20 +288,16 @@ extern "C" int tio_flip3d(const void* x, void* y, int32_t dtype, int32_t batch, 
   }
   const int64_t total = static_cast<int64_t>(shape[0]) * shape[1] * shape[2] * batch * channels;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (es) {
-    case 1: return launch_stream(flip_kernel<1>, a, total, s, "tio_flip3d");
-    case 2: return launch_stream(flip_kernel<2>, a, total, s, "tio_flip3d");
-    case 4: return launch_stream(flip_kernel<4>, a, total, s, "tio_flip3d");
-    default: return launch_stream(flip_kernel<8>, a, total, s, "tio_flip3d");
-  }
+  int status = TIO_OK;
+  const bool known = dispatch_element_size(es, [&](auto size) { status = launch_stream(flip_kernel<decltype(size)::value>, a, total, s, "tio_flip3d"); });
+  return known ? status : fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_flip3d: dtype %d", dtype);
 }
 
 extern "C" int tio_pad3d(const void* x, void* y, int32_t dtype, int32_t batch, int32_t channels, const int32_t in_shape[3],
                          const int32_t padding[6], int32_t mode, double fill, const void* fill_per_element_dev, void* stream) {
   using namespace tio;
   if (in_shape == nullptr || padding == nullptr) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_pad3d: null argument");
-  const int es = dtype_size(dtype);
-  if (es == 0) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_pad3d: dtype %d", dtype);
+  if (!is_known_dtype(dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_pad3d: dtype %d", dtype);
   if (mode < TIO_PAD_CONSTANT || mode > TIO_PAD_CIRCULAR) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_pad3d: mode %d", mode);
   if (batch < 0 || channels < 1) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_pad3d: bad batch / channels");
   PadArgs a{};
@@ -338,25 +317,21 @@ extern "C" int tio_pad3d(const void* x, void* y, int32_t dtype, int32_t batch, i
   if (batch == 0) return TIO_OK;
   if (x == nullptr || y == nullptr) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_pad3d: null data");
   // the constant in the image dtype, like F.pad(value=fill) casts it
-  switch (dtype) {
-    case TIO_F32: { float v = static_cast<float>(fill); uint32_t b; memcpy(&b, &v, 4); a.fill_bits = b; break; }
-    case TIO_F64: { uint64_t b; memcpy(&b, &fill, 8); a.fill_bits = b; break; }
-    case TIO_F16: { _Float16 v = static_cast<_Float16>(static_cast<float>(fill)); uint16_t b; memcpy(&b, &v, 2); a.fill_bits = b; break; }
-    case TIO_BF16: { a.fill_bits = float_to_bf16_bits_host(static_cast<float>(fill)); break; }
-    case TIO_U8: a.fill_bits = static_cast<uint8_t>(static_cast<int64_t>(fill)); break;
-    case TIO_I8: a.fill_bits = static_cast<uint8_t>(static_cast<int8_t>(static_cast<int64_t>(fill))); break;
-    case TIO_I16: a.fill_bits = static_cast<uint16_t>(static_cast<int16_t>(static_cast<int64_t>(fill))); break;
-    case TIO_I32: a.fill_bits = static_cast<uint32_t>(static_cast<int32_t>(static_cast<int64_t>(fill))); break;
-    default: a.fill_bits = static_cast<uint64_t>(static_cast<int64_t>(fill)); break;
-  }
   const int64_t total = static_cast<int64_t>(a.out[0]) * a.out[1] * a.out[2] * batch * channels;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (es) {
-    case 1: return launch_stream(pad_kernel<1>, a, total, s, "tio_pad3d");
-    case 2: return launch_stream(pad_kernel<2>, a, total, s, "tio_pad3d");
-    case 4: return launch_stream(pad_kernel<4>, a, total, s, "tio_pad3d");
-    default: return launch_stream(pad_kernel<8>, a, total, s, "tio_pad3d");
-  }
+  int status = TIO_OK;
+  const bool known = dispatch_dtype(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    using T = typename Elem<DT>::type;
+    T v;
+    if constexpr (DT == TIO_BF16) v = float_to_bf16_bits_host(static_cast<float>(fill));
+    else if constexpr (DT == TIO_F64) v = fill;
+    else if constexpr (DT == TIO_F32 || DT == TIO_F16) v = static_cast<T>(static_cast<float>(fill));
+    else v = static_cast<T>(static_cast<int64_t>(fill));
+    memcpy(&a.fill_bits, &v, sizeof(T));  // the low bytes; the rest stays zero
+    status = launch_stream(pad_kernel<sizeof(T)>, a, total, s, "tio_pad3d");
+  });
+  return known ? status : fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_pad3d: dtype %d", dtype);
 }
 
 // =====================================================================================================================
@@ -438,20 +413,17 @@ extern "C" int tio_bspline_prefilter(const void* x, float* y, int32_t dtype, int
   using namespace tio;
   if (x == nullptr || y == nullptr || shape == nullptr) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_bspline_prefilter: null argument");
   if (order < 2 || order > 7) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_bspline_prefilter: order %d (2 ... 7 are implemented)", order);
-  if (dtype_size(dtype) == 0) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_bspline_prefilter: dtype %d", dtype);
+  if (!is_known_dtype(dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_bspline_prefilter: dtype %d", dtype);
   if (n_bc < 0 || shape[0] < 1 || shape[1] < 1 || shape[2] < 1) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_bspline_prefilter: bad shape");
   if (n_bc == 0) return TIO_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int I = shape[0], J = shape[1], K = shape[2];
   const int64_t n = n_bc * I * J * K;
   const unsigned blocks = static_cast<unsigned>((n + 255) / 256);
-  switch (dtype) {
-#define TIO_CASE(DT) case DT: hipLaunchKernelGGL((bspline_load_kernel<DT>), dim3(blocks), dim3(256), 0, s, x, y, n); break;
-    TIO_CASE(TIO_F32) TIO_CASE(TIO_F64) TIO_CASE(TIO_F16) TIO_CASE(TIO_BF16) TIO_CASE(TIO_U8) TIO_CASE(TIO_I8) TIO_CASE(TIO_I16)
-    TIO_CASE(TIO_I32) TIO_CASE(TIO_I64)
-#undef TIO_CASE
-    default: return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_bspline_prefilter: dtype %d", dtype);
-  }
+  const bool known = dispatch_dtype(dtype, [&](auto dt) {
+    hipLaunchKernelGGL(bspline_load_kernel<decltype(dt)::value>, dim3(blocks), dim3(256), 0, s, x, y, n);
+  });
+  if (!known) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_bspline_prefilter: dtype %d", dtype);
   for (int axis = 0; axis < 3; axis++) {
     const int64_t lines = n / shape[axis];
     hipLaunchKernelGGL(bspline_axis_kernel, dim3(static_cast<unsigned>((lines + 255) / 256)), dim3(256), 0, s, y, lines, I, J, K, axis, order);

@@ -294,7 +294,7 @@ extern "C" int tio_kspace_segment_mix(const void* const* segments, int32_t n_seg
   if (segments == nullptr || bounds == nullptr || shape == nullptr) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_kspace_segment_mix: null argument");
   if (n_segments < 1 || n_segments > TIO_MAX_SEGMENTS)
     return fail(TIO_ERR_INVALID_ARGUMENT, "tio_kspace_segment_mix: %d segments (1..%d)", n_segments, TIO_MAX_SEGMENTS);
-  if (dtype_size(dtype) == 0) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_kspace_segment_mix: dtype %d", dtype);
+  if (!is_known_dtype(dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_kspace_segment_mix: dtype %d", dtype);
   if (batch < 0 || channels < 1 || shape[0] < 1 || shape[1] < 1 || shape[2] < 1)
     return fail(TIO_ERR_INVALID_ARGUMENT, "tio_kspace_segment_mix: bad shape");
   if (bounds[0] != 0 || bounds[n_segments] != shape[0])

@@ -373,16 +373,11 @@ __global__ __launch_bounds__(kThreads) void add_spikes_kernel(SpikeArgs a) {
   }
 }
 
-template <int DT>
-void launch_spikes(const SpikeArgs& a, dim3 grid, hipStream_t s) {
-  hipLaunchKernelGGL(add_spikes_kernel<DT>, grid, dim3(kThreads), 0, s, a);
-}
-
 // the checks the two transforms share; 0 volumes or 0 voxels: *empty
 int check_volume(const char* who, const void* x, const void* y, int32_t dtype, int32_t batch, int32_t channels, const int32_t* shape,
                  bool* empty) {
   *empty = true;
-  if (dtype_size(dtype) == 0) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "%s: dtype %d", who, dtype);
+  if (!is_known_dtype(dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "%s: dtype %d", who, dtype);
   if (shape == nullptr) return fail(TIO_ERR_INVALID_ARGUMENT, "%s: null shape", who);
   if (batch < 0 || channels < 0 || shape[0] < 0 || shape[1] < 0 || shape[2] < 0) return fail(TIO_ERR_INVALID_ARGUMENT, "%s: negative size", who);
   for (int d = 0; d < 3; d++)
@@ -512,16 +507,6 @@ extern "C" int tio_kspace_add_spikes(const void* x, void* y, int32_t dtype, int3
   blocks = blocks > 2048 ? 2048 : blocks;
   const dim3 grid(static_cast<unsigned>(blocks), static_cast<unsigned>(batch * channels));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (dtype) {
-    case TIO_F32: launch_spikes<TIO_F32>(a, grid, s); break;
-    case TIO_F64: launch_spikes<TIO_F64>(a, grid, s); break;
-    case TIO_F16: launch_spikes<TIO_F16>(a, grid, s); break;
-    case TIO_BF16: launch_spikes<TIO_BF16>(a, grid, s); break;
-    case TIO_U8: launch_spikes<TIO_U8>(a, grid, s); break;
-    case TIO_I8: launch_spikes<TIO_I8>(a, grid, s); break;
-    case TIO_I16: launch_spikes<TIO_I16>(a, grid, s); break;
-    case TIO_I32: launch_spikes<TIO_I32>(a, grid, s); break;
-    default: launch_spikes<TIO_I64>(a, grid, s); break;
-  }
-  return check_launch(who);
+  const bool known = dispatch_dtype(dtype, [&](auto dt) { hipLaunchKernelGGL(add_spikes_kernel<decltype(dt)::value>, grid, dim3(kThreads), 0, s, a); });
+  return known ? check_launch(who) : fail(TIO_ERR_UNSUPPORTED_DTYPE, "%s: dtype %d", who, dtype);
 }

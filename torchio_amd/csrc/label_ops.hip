@@ -417,24 +417,11 @@ int launch_components(const void* x_, void* y_, int batch, const int32_t shape[3
 }  // namespace
 }  // namespace tio
 
-#define TIO_FOR_EACH_DTYPE(dtype, CASE) \
-  switch (dtype) {                      \
-    case TIO_F32: CASE(TIO_F32); break; \
-    case TIO_F64: CASE(TIO_F64); break; \
-    case TIO_F16: CASE(TIO_F16); break; \
-    case TIO_BF16: CASE(TIO_BF16); break; \
-    case TIO_U8: CASE(TIO_U8); break;   \
-    case TIO_I8: CASE(TIO_I8); break;   \
-    case TIO_I16: CASE(TIO_I16); break; \
-    case TIO_I32: CASE(TIO_I32); break; \
-    default: CASE(TIO_I64); break;      \
-  }
-
 extern "C" int tio_label_remap(const void* x, void* y, int32_t dtype, int64_t n, const double* keys_dev, const double* values_dev, int32_t n_pairs,
                                int32_t mode, double constant, void* table_dev, void* stream) {
   using namespace tio;
   const int es = dtype_size(dtype);
-  if (dtype < 0 || dtype > TIO_I64 || es == 0) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_label_remap: unknown dtype %d", dtype);
+  if (!is_known_dtype(dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_label_remap: unknown dtype %d", dtype);
   if (n < 0 || n_pairs < 0) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_label_remap: negative size");
   if (n_pairs > TIO_REMAP_MAX_PAIRS) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_label_remap: n_pairs %d beyond %d", n_pairs, TIO_REMAP_MAX_PAIRS);
   if (mode != TIO_REMAP_KEEP && mode != TIO_REMAP_CONSTANT) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_label_remap: unknown mode %d", mode);
@@ -451,27 +438,21 @@ extern "C" int tio_label_remap(const void* x, void* y, int32_t dtype, int64_t n,
     hipLaunchKernelGGL(remap_table_kernel, grid, block, 0, s, static_cast<const int16_t*>(x), static_cast<int16_t*>(y), n, table);
     return check_launch("tio_label_remap");
   }
-#define TIO_REMAP_BYTE(DT) \
-  hipLaunchKernelGGL(remap_byte_kernel<DT>, grid, block, 0, s, static_cast<const Lab<DT>::T*>(x), static_cast<Lab<DT>::T*>(y), n, keys_dev, values_dev, n_pairs, keep, constant)
-#define TIO_REMAP_SEARCH_LDS(DT) \
-  hipLaunchKernelGGL((remap_search_kernel<DT, true>), grid, block, 0, s, static_cast<const Lab<DT>::T*>(x), static_cast<Lab<DT>::T*>(y), n, keys_dev, values_dev, n_pairs, keep, constant)
-#define TIO_REMAP_SEARCH_GLOBAL(DT) \
-  hipLaunchKernelGGL((remap_search_kernel<DT, false>), grid, block, 0, s, static_cast<const Lab<DT>::T*>(x), static_cast<Lab<DT>::T*>(y), n, keys_dev, values_dev, n_pairs, keep, constant)
-  if (dtype == TIO_U8) TIO_REMAP_BYTE(TIO_U8);
-  else if (dtype == TIO_I8) TIO_REMAP_BYTE(TIO_I8);
-  else if (n_pairs <= kRemapLdsPairs) { TIO_FOR_EACH_DTYPE(dtype, TIO_REMAP_SEARCH_LDS) }
-  else { TIO_FOR_EACH_DTYPE(dtype, TIO_REMAP_SEARCH_GLOBAL) }
-#undef TIO_REMAP_BYTE
-#undef TIO_REMAP_SEARCH_LDS
-#undef TIO_REMAP_SEARCH_GLOBAL
-  return check_launch("tio_label_remap");
+  const bool known = dispatch_dtype(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    using T = typename Lab<DT>::T;
+    auto kernel = n_pairs <= kRemapLdsPairs ? remap_search_kernel<DT, true> : remap_search_kernel<DT, false>;
+    if constexpr (DT == TIO_U8 || DT == TIO_I8) kernel = remap_byte_kernel<DT>;
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, static_cast<const T*>(x), static_cast<T*>(y), n, keys_dev, values_dev, n_pairs, keep, constant);
+  });
+  return known ? check_launch("tio_label_remap") : fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_label_remap: unknown dtype %d", dtype);
 }
 
 extern "C" int tio_label_one_hot(const void* x, float* y, int32_t dtype, int32_t batch, int64_t n_spatial, int32_t num_classes, int32_t* status_dev,
                                  void* stream) {
   using namespace tio;
   const int es = dtype_size(dtype);
-  if (dtype < 0 || dtype > TIO_I64 || es == 0) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_label_one_hot: unknown dtype %d", dtype);
+  if (!is_known_dtype(dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_label_one_hot: unknown dtype %d", dtype);
   if (batch < 0 || n_spatial < 0 || num_classes < 0) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_label_one_hot: negative size");
   if (status_dev == nullptr) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_label_one_hot: null status word");
   const bool empty = batch == 0 || n_spatial == 0;
@@ -482,20 +463,17 @@ extern "C" int tio_label_one_hot(const void* x, float* y, int32_t dtype, int32_t
   const int64_t groups = (n_spatial + 3) / 4 * batch;
   const dim3 grid(static_cast<unsigned>((groups + 255) / 256 > 4096 ? 4096 : (groups + 255) / 256)), block(256);
   const bool vec = n_spatial % 4 == 0 && reinterpret_cast<uintptr_t>(x) % (4 * es) == 0 && reinterpret_cast<uintptr_t>(y) % 16 == 0;
-#define TIO_ONE_HOT_VEC(DT) \
-  hipLaunchKernelGGL((one_hot_kernel<DT, true>), grid, block, 0, s, static_cast<const Lab<DT>::T*>(x), y, batch, n_spatial, num_classes, status_dev)
-#define TIO_ONE_HOT_SCALAR(DT) \
-  hipLaunchKernelGGL((one_hot_kernel<DT, false>), grid, block, 0, s, static_cast<const Lab<DT>::T*>(x), y, batch, n_spatial, num_classes, status_dev)
-  if (vec) { TIO_FOR_EACH_DTYPE(dtype, TIO_ONE_HOT_VEC) }
-  else { TIO_FOR_EACH_DTYPE(dtype, TIO_ONE_HOT_SCALAR) }
-#undef TIO_ONE_HOT_VEC
-#undef TIO_ONE_HOT_SCALAR
-  return check_launch("tio_label_one_hot");
+  const bool known = dispatch_dtype(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    const auto kernel = vec ? one_hot_kernel<DT, true> : one_hot_kernel<DT, false>;
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, static_cast<const typename Lab<DT>::T*>(x), y, batch, n_spatial, num_classes, status_dev);
+  });
+  return known ? check_launch("tio_label_one_hot") : fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_label_one_hot: unknown dtype %d", dtype);
 }
 
 extern "C" int tio_label_contour(const void* x, float* y, int32_t dtype, int64_t n_batch_channels, const int32_t shape[3], void* stream) {
   using namespace tio;
-  if (dtype < 0 || dtype > TIO_I64 || dtype_size(dtype) == 0) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_label_contour: unknown dtype %d", dtype);
+  if (!is_known_dtype(dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_label_contour: unknown dtype %d", dtype);
   if (shape == nullptr) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_label_contour: null shape");
   if (n_batch_channels < 0 || shape[0] < 0 || shape[1] < 0 || shape[2] < 0) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_label_contour: negative size");
   if (n_batch_channels == 0 || shape[0] == 0 || shape[1] == 0 || shape[2] == 0) return TIO_OK;
@@ -505,10 +483,10 @@ extern "C" int tio_label_contour(const void* x, float* y, int32_t dtype, int64_t
   if (blocks >= (int64_t{1} << 31)) return fail(TIO_ERR_UNSUPPORTED_CONFIG, "tio_label_contour: too many tiles");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const dim3 grid(static_cast<unsigned>(blocks)), block(kContourTJ * kContourTK);
-#define TIO_CONTOUR(DT) hipLaunchKernelGGL(contour_kernel<DT>, grid, block, 0, s, x, y, shape[0], shape[1], shape[2], tiles_j, tiles_k)
-  TIO_FOR_EACH_DTYPE(dtype, TIO_CONTOUR)
-#undef TIO_CONTOUR
-  return check_launch("tio_label_contour");
+  const bool known = dispatch_dtype(dtype, [&](auto dt) {
+    hipLaunchKernelGGL(contour_kernel<decltype(dt)::value>, grid, block, 0, s, x, y, shape[0], shape[1], shape[2], tiles_j, tiles_k);
+  });
+  return known ? check_launch("tio_label_contour") : fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_label_contour: unknown dtype %d", dtype);
 }
 
 extern "C" int64_t tio_keep_largest_workspace_bytes(int32_t batch, const int32_t shape[3], int32_t n_labels) {

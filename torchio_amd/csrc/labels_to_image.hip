@@ -202,7 +202,7 @@ extern "C" int tio_labels_to_image(const void* labels, int32_t dtype, int32_t ba
   using namespace tio;
   const char* who = "tio_labels_to_image";
   const int es = dtype_size(dtype);
-  if (dtype < 0 || dtype > TIO_I64 || es == 0) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "%s: unknown dtype %d", who, dtype);
+  if (!is_known_dtype(dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "%s: unknown dtype %d", who, dtype);
   if (batch < 0 || channels < 0 || n_spatial < 0 || n_keys < 0) return fail(TIO_ERR_INVALID_ARGUMENT, "%s: negative size", who);
   if (n_keys > TIO_REMAP_MAX_PAIRS) return fail(TIO_ERR_INVALID_ARGUMENT, "%s: n_keys %d beyond %d", who, n_keys, TIO_REMAP_MAX_PAIRS);
   if (batch > 65535) return fail(TIO_ERR_UNSUPPORTED_CONFIG, "%s: more than 65535 batch elements", who);
@@ -228,19 +228,8 @@ extern "C" int tio_labels_to_image(const void* labels, int32_t dtype, int32_t ba
   }
   const int64_t blocks = (n_spatial / 4 + 2 + kThreads - 1) / kThreads;  // (a row off the quad touches up to n / 4 + 2 blocks)
   const dim3 grid(static_cast<unsigned>(blocks > kBlocksPerRow ? kBlocksPerRow : blocks), static_cast<unsigned>(batch));
-#define TIO_LABELS_TO_IMAGE(DT) \
-  launch<DT>(labels, channels, n_spatial, keys_dev, n_keys, mean_dev, std_dev, params_batched != 0, out, philox_seed, base_dev, base_key, grid, s)
-  switch (dtype) {
-    case TIO_F32: TIO_LABELS_TO_IMAGE(TIO_F32); break;
-    case TIO_F64: TIO_LABELS_TO_IMAGE(TIO_F64); break;
-    case TIO_F16: TIO_LABELS_TO_IMAGE(TIO_F16); break;
-    case TIO_BF16: TIO_LABELS_TO_IMAGE(TIO_BF16); break;
-    case TIO_U8: TIO_LABELS_TO_IMAGE(TIO_U8); break;
-    case TIO_I8: TIO_LABELS_TO_IMAGE(TIO_I8); break;
-    case TIO_I16: TIO_LABELS_TO_IMAGE(TIO_I16); break;
-    case TIO_I32: TIO_LABELS_TO_IMAGE(TIO_I32); break;
-    default: TIO_LABELS_TO_IMAGE(TIO_I64); break;
-  }
-#undef TIO_LABELS_TO_IMAGE
-  return check_launch(who);
+  const bool known = dispatch_dtype(dtype, [&](auto dt) {
+    launch<decltype(dt)::value>(labels, channels, n_spatial, keys_dev, n_keys, mean_dev, std_dev, params_batched != 0, out, philox_seed, base_dev, base_key, grid, s);
+  });
+  return known ? check_launch(who) : fail(TIO_ERR_UNSUPPORTED_DTYPE, "%s: unknown dtype %d", who, dtype);
 }

@@ -30,12 +30,6 @@ namespace {
 constexpr int PERMUTE_TILE = 64;
 constexpr int PERMUTE_PITCH = PERMUTE_TILE + 1;
 
-template <int ES>
-struct RawOf {
-  using type = typename std::conditional<ES == 1, uint8_t, typename std::conditional<ES == 2, uint16_t,
-               typename std::conditional<ES == 4, uint32_t, uint64_t>::type>::type>::type;
-};
-
 struct PermuteRowArgs {
   const void* x;
   void* y;
@@ -47,7 +41,7 @@ struct PermuteRowArgs {
 
 template <int ES>
 __global__ __launch_bounds__(256) void permute_rows_kernel(const PermuteRowArgs a) {
-  using RAW = typename RawOf<ES>::type;
+  using RAW = typename RawBits<ES>::type;
   const int64_t n = static_cast<int64_t>(a.out[0]) * a.out[1] * a.out[2];
   const int64_t total = n * a.n_bc;
   for (int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; t < total;
@@ -80,7 +74,7 @@ struct PermuteTileArgs {
 
 template <int ES>
 __global__ __launch_bounds__(256) void permute_tile_kernel(const PermuteTileArgs a) {
-  using RAW = typename RawOf<ES>::type;
+  using RAW = typename RawBits<ES>::type;
   using CELL = typename std::conditional<ES == 8, uint64_t, uint32_t>::type;
   __shared__ CELL tile[PERMUTE_TILE][PERMUTE_PITCH];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -129,7 +123,7 @@ extern "C" int tio_permute3d(const void* x, void* y, int32_t dtype, int32_t batc
   using namespace tio;
   if (in_shape == nullptr || perm == nullptr) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_permute3d: null shape or perm");
   const int es = dtype_size(dtype);
-  if (es == 0) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_permute3d: dtype %d", dtype);
+  if (!is_known_dtype(dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_permute3d: dtype %d", dtype);
   if (batch < 0) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_permute3d: negative batch");
   if (channels < 1) return fail(TIO_ERR_INVALID_ARGUMENT, "tio_permute3d: channels must be >= 1");
   int seen = 0;
@@ -153,12 +147,9 @@ extern "C" int tio_permute3d(const void* x, void* y, int32_t dtype, int32_t batc
     for (int d = 0; d < 3; d++) { a.in[d] = in_shape[d]; a.out[d] = out[d]; }
     int64_t blocks = (n * n_bc + 255) / 256;
     if (blocks > 256 * 32) blocks = 256 * 32;
-    switch (es) {
-      case 1: return launch_permute(permute_rows_kernel<1>, a, blocks, s);
-      case 2: return launch_permute(permute_rows_kernel<2>, a, blocks, s);
-      case 4: return launch_permute(permute_rows_kernel<4>, a, blocks, s);
-      default: return launch_permute(permute_rows_kernel<8>, a, blocks, s);
-    }
+    int status = TIO_OK;
+    const bool known = dispatch_element_size(es, [&](auto size) { status = launch_permute(permute_rows_kernel<decltype(size)::value>, a, blocks, s); });
+    return known ? status : fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_permute3d: dtype %d", dtype);
   }
 
   // the tile: input axis 2 (k) x input axis perm[2] (m); r is the input axis that is left
@@ -177,10 +168,7 @@ extern "C" int tio_permute3d(const void* x, void* y, int32_t dtype, int32_t batc
   a.flip_k = (flip_mask >> 2) & 1; a.flip_m = (flip_mask >> axis_m) & 1; a.flip_r = (flip_mask >> axis_r) & 1;
   int64_t blocks = a.n_tiles;
   if (blocks > (1 << 20)) blocks = 1 << 20;  // the blocks stride over the rest
-  switch (es) {
-    case 1: return launch_permute(permute_tile_kernel<1>, a, blocks, s);
-    case 2: return launch_permute(permute_tile_kernel<2>, a, blocks, s);
-    case 4: return launch_permute(permute_tile_kernel<4>, a, blocks, s);
-    default: return launch_permute(permute_tile_kernel<8>, a, blocks, s);
-  }
+  int status = TIO_OK;
+  const bool known = dispatch_element_size(es, [&](auto size) { status = launch_permute(permute_tile_kernel<decltype(size)::value>, a, blocks, s); });
+  return known ? status : fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_permute3d: dtype %d", dtype);
 }

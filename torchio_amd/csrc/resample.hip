@@ -680,14 +680,6 @@ auto with_bools(F f, bool first, Rest... rest) {
   return first ? with_bools([&](auto... c) { return f(std::true_type{}, c...); }, rest...)
                : with_bools([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
 }
-// ... and an element size of 1, 2, 4 or 8 bytes
-template <typename F>
-void with_element_size(int es, F f) {
-  if (es == 1) f(std::integral_constant<int, 1>{});
-  else if (es == 2) f(std::integral_constant<int, 2>{});
-  else if (es == 4) f(std::integral_constant<int, 4>{});
-  else f(std::integral_constant<int, 8>{});
-}
 
 using RowsKernel = void (*)(ResampleArgs);               // resample_kernel
 using BrickKernel = void (*)(ResampleArgs, const int*);  // resample_tile_kernel, resample_planned_kernel
@@ -877,7 +869,7 @@ int sort_images(int32_t n_images, const tio_resample_image* images, const EnvSwi
     const tio_resample_image& s = images[i];
     if (s.in == nullptr || s.out == nullptr || s.channels < 1)
       return fail(TIO_ERR_INVALID_ARGUMENT, "tio_resample3d: image %d has null data or no channels", i);
-    if (dtype_size(s.dtype) == 0) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_resample3d: image %d dtype %d", i, s.dtype);
+    if (!is_known_dtype(s.dtype)) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_resample3d: image %d dtype %d", i, s.dtype);
     if (s.interp != TIO_NEAREST && s.interp != TIO_LINEAR && s.interp != TIO_LABEL_PV && s.interp != TIO_LINEAR_ADJOINT &&
         TIO_BSPLINE_ORDER(s.interp) == 0)
       return fail(TIO_ERR_INVALID_ARGUMENT, "tio_resample3d: image %d interp %d", i, s.interp);
@@ -1045,10 +1037,11 @@ struct LabelRide {
   int es = 0;  // element size of the pending label channel (0: none)
   unsigned blocks = 0, lds = 0;
 };
-void launch_nearest_exact(const NearestArgs& nn, int es, unsigned blocks, unsigned lds, hipStream_t s) {
-  with_element_size(es, [&](auto size) {
+int launch_nearest_exact(const NearestArgs& nn, int es, unsigned blocks, unsigned lds, hipStream_t s) {
+  const bool known = dispatch_element_size(es, [&](auto size) {
     with_bools([&](auto elastic) { hipLaunchKernelGGL((resample_nearest_exact_kernel<elastic.value, size.value>), dim3(blocks), dim3(256), lds, s, nn); }, nn.cp != nullptr);
   });
+  return known ? TIO_OK : fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_resample3d: label elements of %d bytes", es);
 }
 
 // nearest images (label maps): one launch per element size present.  `short_div`: the float group's gate of the exact coordinates; `floats_alone`: float images follow and
@@ -1076,13 +1069,14 @@ int launch_nearest(NearestArgs& nn, bool short_div, bool floats_alone, const Env
     if (exact && narrow && env.lean_label != 0 && nn.n_images == 1 && nn.img[0].channels == 1 && es <= 4 && floats_alone) {
       label->es = es; label->blocks = blocks; label->lds = exact_lds;  // ONE plain label channel beside float images: it may ride
     } else if (exact && narrow) {
-      launch_nearest_exact(nn, es, blocks, exact_lds, s);
+      if (const int st = launch_nearest_exact(nn, es, blocks, exact_lds, s)) return st;
     } else {
-      with_element_size(es, [&](auto size) {
+      const bool known = dispatch_element_size(es, [&](auto size) {
         with_bools([&](auto elastic, auto wave_rows) {
           hipLaunchKernelGGL((resample_nearest_kernel<elastic.value, size.value, wave_rows.value ? 4 : 16, wave_rows.value ? 64 : 16, 16>), dim3(blocks), dim3(256), 0, s, nn);
         }, nn.cp != nullptr, rows);
       });
+      if (!known) return fail(TIO_ERR_UNSUPPORTED_DTYPE, "tio_resample3d: label elements of %d bytes", es);
     }
   }
   return TIO_OK;

@@ -55,12 +55,6 @@ struct NearestArgs {
 // (exact_voxel_coords — the exact coordinate chain of ONE voxel — lives in resample_exact_chain.hpp: the FAST float kernels
 // use it as well, for the fill decision of voxels whose in-bounds weight is within rounding of 1/2)
 
-template <int ES> struct NearestBits;
-template <> struct NearestBits<1> { typedef uint8_t type; };
-template <> struct NearestBits<2> { typedef uint16_t type; };
-template <> struct NearestBits<4> { typedef uint32_t type; };
-template <> struct NearestBits<8> { typedef uint64_t type; };
-
 template <int ES> struct NearestCarrier { typedef uint32_t type; };  // what a loaded element travels in (a whole register)
 template <> struct NearestCarrier<8> { typedef uint64_t type; };
 
@@ -110,7 +104,7 @@ __device__ __forceinline__ typename NearestCarrier<ES>::type nearest_fill_bits(i
 // for volumes narrower than that.  The host only launches it for I * J <= 2^24 and K < 2^24 (unsigned 24-bit multiply-adds).
 template <bool ELASTIC_POSSIBLE, int ES, int TJ, int TK, int TI>
 __global__ __launch_bounds__(256) void resample_nearest_kernel(const NearestArgs a) {
-  typedef typename NearestBits<ES>::type bits_t;
+  typedef typename RawBits<ES>::type bits_t;
   static_assert(TJ * TK == 256 && (TK & (TK - 1)) == 0 && (TI == 16 || TI == 32), "one thread per column of the brick");
   // (TI = 32 — the prologue spread over twice the voxels — was measured: 128 VGPRs, four waves per SIMD; int16 + elastic
   //  0.330 -> 0.313 ms, uint8 affine 0.246 -> 0.365 ms: the launch code instantiates 16 only)
@@ -397,7 +391,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t nearest_channel_rsrc(const Nea
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(src), 0, static_cast<int>(static_cast<unsigned>(n_in) * ES), 0x00020000);
 }
 template <int ES>
-__device__ __forceinline__ typename NearestBits<ES>::type nearest_buffer_load(__amdgpu_buffer_rsrc_t rsrc, unsigned off) {
+__device__ __forceinline__ typename RawBits<ES>::type nearest_buffer_load(__amdgpu_buffer_rsrc_t rsrc, unsigned off) {
   if constexpr (ES == 1) return __builtin_amdgcn_raw_buffer_load_b8(rsrc, off, 0, 0);
   else if constexpr (ES == 2) return __builtin_amdgcn_raw_buffer_load_b16(rsrc, off, 0, 0);
   else if constexpr (ES == 4) return __builtin_amdgcn_raw_buffer_load_b32(rsrc, off, 0, 0);
@@ -409,7 +403,7 @@ __device__ __forceinline__ typename NearestBits<ES>::type nearest_buffer_load(__
 
 template <bool ELASTIC_POSSIBLE, int ES>
 __global__ __launch_bounds__(256, 3) void resample_nearest_exact_kernel(const NearestArgs a) {
-  typedef typename NearestBits<ES>::type bits_t;
+  typedef typename RawBits<ES>::type bits_t;
   typedef typename NearestCarrier<ES>::type carrier_t;
   constexpr int TI = 16, TJ = 4, TK = 64;
   {

@@ -155,11 +155,9 @@ extern "C" int tio_swap_patches(const void* x, void* y, int32_t element_bytes, i
   if (volumes > (int64_t{1} << 62) / (2 * static_cast<int64_t>(s_max)) / g.blocks_per_box) return fail(TIO_ERR_UNSUPPORTED_CONFIG, "%s: too many box voxels", who);
   g.tasks = volumes * s_max * 2 * g.blocks_per_box;
   const dim3 grid(static_cast<unsigned>(g.tasks < (1 << 20) ? g.tasks : (1 << 20))), block(256);
-  switch (element_bytes) {
-    case 1: hipLaunchKernelGGL(swap_gather_kernel<uint8_t>, grid, block, 0, s, static_cast<const uint8_t*>(x), static_cast<uint8_t*>(y), origins_dev, counts_dev, g); break;
-    case 2: hipLaunchKernelGGL(swap_gather_kernel<uint16_t>, grid, block, 0, s, static_cast<const uint16_t*>(x), static_cast<uint16_t*>(y), origins_dev, counts_dev, g); break;
-    case 4: hipLaunchKernelGGL(swap_gather_kernel<uint32_t>, grid, block, 0, s, static_cast<const uint32_t*>(x), static_cast<uint32_t*>(y), origins_dev, counts_dev, g); break;
-    default: hipLaunchKernelGGL(swap_gather_kernel<uint64_t>, grid, block, 0, s, static_cast<const uint64_t*>(x), static_cast<uint64_t*>(y), origins_dev, counts_dev, g); break;
-  }
-  return check_launch(who);
+  const bool known = dispatch_element_size(element_bytes, [&](auto size) {
+    using T = typename RawBits<decltype(size)::value>::type;
+    hipLaunchKernelGGL(swap_gather_kernel<T>, grid, block, 0, s, static_cast<const T*>(x), static_cast<T*>(y), origins_dev, counts_dev, g);
+  });
+  return known ? check_launch(who) : fail(TIO_ERR_UNSUPPORTED_DTYPE, "%s: elements of %d bytes (1, 2, 4 or 8)", who, element_bytes);
 }
