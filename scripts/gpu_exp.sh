@@ -68,12 +68,12 @@ for step in "$@"; do
       timeout 900 python -m pytest tests/test_gpu_ahead.py tests/test_gpu_resample_planned.py tests/test_gpu_full_size.py -m gpu -q --tb=short -x 2>&1 | tail -60 > gpurun_out/r4_gpu_tests_ahead.txt
       grep -v "Warning\|^$\|warnings.html\|^  " gpurun_out/r4_gpu_tests_ahead.txt | tail -40 ;;
     ab_ahead)
-      # the side stream (uploads + brick plans ahead of the data) and the announced minimum, on and off, alternating
+      # the side stream (uploads + brick plans ahead of the data), on and off, alternating
       L=gpurun_out/r4_ab_ahead.log; : > $L
       for rep in 1 2 3; do
-        for off in 0 3 1 2; do
-          TIO_NO_AHEAD_STREAM=$((off & 1)) TIO_NO_ANNOUNCED_MIN=$((off >> 1)) timeout 200 python bench.py --full --steps 60 --no-cpu-baseline --no-aten-baseline --no-other-configs --no-mode-matrix 2>/dev/null |
-            python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('off(1=stream,2=announced min)=$off', round(d['value'],1), 'vol/s', round(d['ms_per_step'],4), 'ms/step host', round(d['host_enqueue_ms_per_step'],3), 'launch_ms', round(d['roofline']['launch_ms'],4))" >> $L
+        for off in 0 1; do
+          TIO_NO_AHEAD_STREAM=$off timeout 200 python bench.py --full --steps 60 --no-cpu-baseline --no-aten-baseline --no-other-configs --no-mode-matrix 2>/dev/null |
+            python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('TIO_NO_AHEAD_STREAM=$off', round(d['value'],1), 'vol/s', round(d['ms_per_step'],4), 'ms/step host', round(d['host_enqueue_ms_per_step'],3), 'launch_ms', round(d['roofline']['launch_ms'],4))" >> $L
         done
       done
       cat $L ;;

@@ -226,6 +226,41 @@ def test_concurrent_streams_do_not_share_staging_buffers(hip):
                 assert torch.equal(expected.view(torch.int32), got.view(torch.int32)), (seed, repeat)
 
 
+def test_a_plan_started_ahead_for_another_draw_is_refused_and_gives_its_buffer_back(hip):
+    """`prefetch_plan` hands a pinned buffer of the thread's plan ring to a native job; a draw of another count is refused on
+    the host (nothing is launched), by `randn` ("not the next one") and by `_device_plan` behind `add_noise` ("was started
+    ahead") — and either way the job has ended and holds no buffer any more.  (Before the plan started ahead had one way
+    out, `randn`'s refusal left the buffer lent for the life of the thread: the first of the two ring assertions failed.)"""
+    from torchio_amd import noise_stream, ops
+
+    count = ops.HostNormalStream.DEVICE_DRAW_MIN
+    assert count == 1 << 20
+    ring = noise_stream._PLAN_RING
+    device = torch.cuda.current_device()
+    previous = ops.get_noise_plan()
+    ops.set_noise_plan("host")  # (with the device's plan nothing is started ahead for whole groups of 16)
+    try:
+        stream = ops.HostNormalStream(31)
+        stream.prefetch_plan(count, "cuda")
+        assert stream._prefetched is not None and sum(buffer.lent for buffer in ring.buffers(device)) == 1
+        with pytest.raises(ops.EngineError, match="not the next one"):
+            stream.randn((2 * count,), "cuda")
+        assert stream._prefetched is None and not any(buffer.lent for buffer in ring.buffers(device))
+
+        stream = ops.HostNormalStream(31)
+        stream.prefetch_plan(count, "cuda")
+        assert stream._prefetched is not None and sum(buffer.lent for buffer in ring.buffers(device)) == 1
+        with pytest.raises(ops.EngineError, match="was started ahead"):
+            stream.add_noise(torch.zeros(2 * count, device="cuda"), 0.0, 1.0)
+        assert stream._prefetched is None and not any(buffer.lent for buffer in ring.buffers(device))
+
+        drawn = ops.HostNormalStream(31).randn((count,), "cuda")
+    finally:
+        ops.set_noise_plan(previous)
+    expected = torch.randn(count, generator=torch.Generator().manual_seed(31))
+    assert torch.equal(expected.view(torch.int32), drawn.cpu().view(torch.int32))
+
+
 def _untemper(y: "np.ndarray") -> "np.ndarray":
     """Inverse of mt19937's tempering on uint32 arrays (a bijection: every 24-bit uniform can be asked for)."""
     import numpy as np

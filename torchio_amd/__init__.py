@@ -22,15 +22,15 @@ from .data import LabelMap
 from .data import ScalarImage
 from .data import Subject
 from .data import SubjectsBatch
-from .ops import calibrate_draw_policy
-from .ops import get_draw_policy
-from .ops import get_noise_plan
-from .ops import set_noise_plan
+from .noise_stream import get_noise_plan
+from .noise_stream import set_noise_plan
 from .ops import get_resample_precision
-from .ops import set_draw_policy
 from .ops import get_stencil_precision
 from .ops import set_resample_precision
 from .ops import set_stencil_precision
+from .streams import calibrate_draw_policy
+from .streams import get_draw_policy
+from .streams import set_draw_policy
 from .transforms import Affine
 from .transforms import Anisotropy
 from .transforms import AppliedTransform

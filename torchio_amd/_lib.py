@@ -24,6 +24,10 @@ class HipLibraryError(RuntimeError):
     """The HIP extension is missing, stale or failed to load."""
 
 
+class EngineError(RuntimeError):
+    """A ``tio_*`` call returned a non-zero status."""
+
+
 def load():
     """Return ``(CDLL, {name: function})`` for libtio_hip.so, loading it once."""
     global _lib, _functions

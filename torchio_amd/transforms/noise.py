@@ -25,6 +25,7 @@ from torch import Tensor
 from .. import ops
 from ..data import _pending
 from ..data.batch import SubjectsBatch
+from ..noise_stream import HostNormalStream
 from .parameter_range import to_nonneg_range
 from .parameter_range import to_range
 from .transform import IntensityTransform
@@ -49,10 +50,10 @@ def _reference_stream_images(transform, batch: SubjectsBatch):
     """The tensors the reference-identical stream would be drawn for on the device, or None (another mode / host images).
     (A module function: `Noise.apply_transform` also runs with the REFERENCE's transform instance as `self`, reference_binding.)"""
     images = transform._get_images(batch)
-    if _NOISE_RNG != "reference" or not images or os.environ.get("TIO_HOST_RNG", "1") == "0":
+    if _NOISE_RNG != "reference" or not images:
         return None
     tensors = [img._data if hasattr(img, "_data") else img.data for img in images.values()]  # (shape / device: pending stages keep both)
-    if all(t.is_cuda and ops.HostNormalStream.takes(t.shape) for t in tensors):
+    if all(t.is_cuda and HostNormalStream.takes(t.shape) for t in tensors):
         return tensors
     return None
 
@@ -104,7 +105,7 @@ class Noise(IntensityTransform):
         first = tensors[0]
         if first.dtype not in (torch.float32, torch.float64) or not first.is_contiguous():
             return  # (another dtype is converted first: its draw keeps the count, but stay on the simple road)
-        stream = ops.HostNormalStream(params["seed"])
+        stream = HostNormalStream(params["seed"])
         stream.prefetch_plan(first.numel(), first.device)
         # (the entry holds the parameters object itself — its id cannot be reused while the entry lives — and the seed
         # it was started for; `_abandon_prefetch`, called by Compose whatever happens to the children in between, drops an
@@ -123,14 +124,14 @@ class Noise(IntensityTransform):
         engine = ops.engine()
         images = self._get_images(batch)
         # the reference-identical stream for device-resident images: the same draws as `torch.randn(..., generator=generator)`
-        # below — made on the device from the host's plan of the state chain, or on all host cores (ops.HostNormalStream);
+        # below — made on the device from the host's plan of the state chain, or on all host cores (noise_stream.HostNormalStream);
         # one stream object = the one generator of this call
         stream = None
         ahead = _STREAMS_AHEAD.pop(id(params), None)  # (started by `_prefetch`: its first plan is being computed, or done)
         if ahead is not None and ahead[0] is params and ahead[1] == int(seed):
             stream = ahead[2]
         if stream is None and _reference_stream_images(self, batch) is not None:
-            stream = ops.HostNormalStream(seed)
+            stream = HostNormalStream(seed)
         for index, img_batch in enumerate(images.values()):
             queue = getattr(img_batch, "_pending", None)  # foreign containers (reference_binding) never defer
             if (

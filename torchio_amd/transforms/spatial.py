@@ -33,6 +33,7 @@ from torch import Tensor
 from torch.distributions import Distribution
 
 from .. import ops
+from .. import streams
 from ..data.affine import AffineMatrix
 from ..data.batch import ImagesBatch
 from ..data.batch import SubjectsBatch
@@ -372,14 +373,14 @@ class Spatial(SpatialTransform):
 
     def _prefetch(self, batch: SubjectsBatch, params: dict[str, Any]) -> None:
         """Draw-ahead road (Compose): mapping, control points, flags and the brick plan of the fused launch depend on the drawn
-        parameters and the batch's geometry only — they go to the device on the side stream (`ops.ahead_stream`) now, while
+        parameters and the batch's geometry only — they go to the device on the side stream (`streams.ahead_stream`) now, while
         the children before this one are still being enqueued (or their kernels still run); `apply_transform` picks them up."""
         selected = params.get("selected_images", [])
         if not selected or not isinstance(params, LazyParams):
             return
         first = batch.images[selected[0]]
         tensor = first._data if hasattr(first, "_data") else first.data
-        side = ops.ahead_stream(tensor.device) if tensor.is_cuda else None
+        side = streams.ahead_stream(tensor.device) if tensor.is_cuda else None
         if side is None:
             return
         try:
@@ -387,7 +388,7 @@ class Spatial(SpatialTransform):
             matrix, field, displacement, per_sample = _resolve_spatial_params(params)
             if target_space is None and matrix is None and field is None and displacement is None and per_sample is None:
                 return
-            ahead = ops.Ahead()
+            ahead = streams.Ahead()
             with torch.cuda.stream(side):
                 geometry = _prepare_launch_geometry(
                     first, tensor.device, target_space=target_space, affine_matrix=matrix, control_points=field,
