@@ -28,6 +28,7 @@ DEFAULT_FILES = [
     "test_flip.py", "test_pad.py", "test_crop.py", "test_compose.py", "test_one_of.py", "test_some_of.py", "test_inverse.py", "test_parameter_range.py",
     "test_patches.py", "test_queue.py", "test_affine.py", "test_batch.py", "test_per_instance.py", "test_vectorization.py",
     "test_crop_or_pad.py", "test_ensure_shape_multiple.py", "test_to_reference_space.py", "test_copy_affine.py",
+    "test_to.py", "test_lambda_transform.py",
 ]
 
 

@@ -43,6 +43,7 @@ class LazyCopyScope:
 
     def borrow(self, holder, tensor):
         self._borrowed.append((holder, tensor))
+        holder._borrowed_tensor = tensor  # for a transform that writes in place (Lambda): see `is_borrowed`
         return tensor
 
     def materialise(self) -> None:
@@ -57,4 +58,12 @@ class LazyCopyScope:
                 # a transform handed back a VIEW of the borrowed tensor (Crop slices, a user transform that
                 # writes ``img.data[...]`` in place and re-assigns it): still the caller's memory
                 holder._data = current.clone()
+            holder._borrowed_tensor = None
         self._borrowed.clear()
+
+
+def is_borrowed(holder) -> bool:
+    """True while *holder*'s tensor is, or is a view of, a tensor it shares with the caller (``LazyCopyScope.borrow``) —
+    until a transform has replaced it or the scope has been materialised.  Whoever wants to write it in place clones first."""
+    tensor = getattr(holder, "_borrowed_tensor", None)
+    return tensor is not None and _shares_storage(getattr(holder, "_data", None), tensor)

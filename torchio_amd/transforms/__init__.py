@@ -10,6 +10,7 @@ from .ghosting import Ghosting
 from .histogram_standardization import HistogramStandardization
 from .inverse import apply_inverse_transform
 from .inverse import get_inverse_transform
+from .lambda_transform import Lambda
 from .labels import Contour
 from .labels import KeepLargestComponent
 from .labels import OneHot
@@ -43,6 +44,7 @@ from .spatial import Resample
 from .spatial import Spatial
 from .spike import Spike
 from .swap import Swap
+from .to import To
 from .transform import AppliedTransform
 from .transform import IntensityTransform
 from .transform import SpatialTransform
@@ -50,7 +52,7 @@ from .transform import Transform
 
 __all__ = [
     "Affine", "Anisotropy", "AppliedTransform", "BiasField", "Blur", "Choice", "Clamp", "Compose", "Contour", "CopyAffine", "Crop", "CropOrPad", "ElasticDeformation", "EnsureShapeMultiple", "Flip", "Gamma", "Ghosting",
-    "HistogramStandardization", "IntensityTransform", "KeepLargestComponent", "LabelsToImage", "Mask", "Motion", "Noise", "Normalize", "OneHot", "OneOf", "Pad", "RemapLabels", "RemoveLabels", "Reorient", "Resample", "RescaleIntensity",
-    "Resize", "SequentialLabels", "SomeOf", "Spatial", "SpatialTransform", "Spike", "Standardize", "Swap", "ToReferenceSpace", "Transform", "Transpose", "ZNormalization",
+    "HistogramStandardization", "IntensityTransform", "KeepLargestComponent", "LabelsToImage", "Lambda", "Mask", "Motion", "Noise", "Normalize", "OneHot", "OneOf", "Pad", "RemapLabels", "RemoveLabels", "Reorient", "Resample", "RescaleIntensity",
+    "Resize", "SequentialLabels", "SomeOf", "Spatial", "SpatialTransform", "Spike", "Standardize", "Swap", "To", "ToReferenceSpace", "Transform", "Transpose", "ZNormalization",
     "apply_inverse_transform", "get_inverse_transform", "get_noise_rng", "set_noise_rng",
 ]
