@@ -967,6 +967,50 @@ int tio_mt19937_add_noise_device(const uint32_t* plan_host, const uint32_t* plan
                                  void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* PCA over the channel axis (additive to ABI 18, HIP only)                  */
+/* ------------------------------------------------------------------------ */
+/*
+ * PCA (transforms/intensity/pca.py:83-140 _pca_single).  The reference's first step is `tensor.float()` (pca.py:102), so
+ * these entry points take float32 data and nothing else: the caller casts where the reference does.  x is a dense
+ * (batch, channels, voxels) tensor at any 4-byte boundary, 1 <= channels <= TIO_PCA_MAX_CHANNELS, voxels >= 1.
+ * batch == 0: TIO_OK, nothing done.
+ */
+#define TIO_PCA_MAX_CHANNELS 1024
+
+/*
+ * The centring and the covariance that torch.pca_lowrank derives its basis from (pca.py:105-109: `flat.mean(dim=0)`,
+ * `flat - mean`, and the matrix products inside pca_lowrank), exact instead of sketched, in ONE read of x:
+ *   mean[b, c]       = sum_v x[b, c, v] / voxels                                   (batch, channels) float64
+ *   scatter[b, i, j] = sum_v (x[b, i, v] - mean[b, i]) (x[b, j, v] - mean[b, j])   (batch, channels, channels) float64,
+ *                      symmetric bit for bit, both triangles written
+ * Accumulated in float64 on the matrix cores around the pivot x[b, c, 0] and corrected for the pivot at the end, so a mean
+ * far above the deviation costs nothing.  Per-chunk partials go to fixed slots of the workspace and are added in ascending
+ * order, no float atomics: two calls on the same input return the same bits.
+ *   workspace_dev  device, 8-byte aligned, at least tio_channel_scatter_workspace_bytes(batch, channels, voxels) bytes;
+ *                  it may hold anything and may be reused by the next call on the same stream
+ * batch > 65535: TIO_ERR_UNSUPPORTED_CONFIG.
+ */
+int64_t tio_channel_scatter_workspace_bytes(int32_t batch, int32_t channels, int64_t voxels); /* -1: bad sizes */
+/* HOST only, nothing is enqueued: how tio_channel_scatter splits that call.  out = { chunks of voxels, voxels per chunk
+ * (a multiple of 16), tile pairs (16 x 16 channels) per block, blocks of the accumulating launch }. */
+int tio_channel_scatter_plan(int32_t batch, int32_t channels, int64_t voxels, int32_t out[4]);
+int tio_channel_scatter(const float* x, int32_t batch, int32_t channels, int64_t voxels, double* mean, double* scatter,
+                        void* workspace_dev, int64_t workspace_bytes, void* stream);
+
+/*
+ * The rest of _pca_single in one pass (pca.py:106 `flat - mean`, :111 `centered @ v`, :119 `/ std`, :123 `/ first_std`,
+ * :127 `(projected - lo) / (hi - lo)`, :130 `.clamp(0, 1)`), the scalings folded into the weights by the caller:
+ *   y[b, k, v] = sum_c weights[b, k, c] (x[b, c, v] - center[b, c]) + offset[b, k],   clamped to [0, 1] when clip != 0
+ * center_dev (batch, channels), weights_dev (batch, components, channels), offset_dev (batch, components): float32 on the
+ * device; y (batch, components, voxels) float32, 1 <= components <= channels.  The difference is rounded to float32 before
+ * the product, as in the reference, one fma per term in ascending channel order.  A NaN stays NaN through the clamp
+ * (torch.clamp).  Components are taken 8 at a time; x is read once per 8.  batch > 65535: TIO_ERR_UNSUPPORTED_CONFIG.
+ */
+int tio_channel_project(const float* x, int32_t batch, int32_t channels, int64_t voxels, const float* center_dev,
+                        const float* weights_dev, const float* offset_dev, int32_t components, int32_t clip, float* y,
+                        void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* Introspection                                                             */
 /* ------------------------------------------------------------------------ */
 int tio_abi_version(void);

@@ -272,8 +272,18 @@ HIP_ONLY_PROTOTYPES = {
     ),
     # Reorient / Transpose: the tiled axis permutation (additive to ABI 18): no CPU restatement either
     "permute3d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _I32x3, _I32x3, C.c_int32, C.c_void_p]),
+    # PCA: float64 channel scatter on the matrix cores and the fused projection (additive to ABI 18): float32 data only, no CPU
+    # restatement either
+    "channel_scatter_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64]),
+    "channel_scatter_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32)]),
+    "channel_scatter": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "channel_project": (
+        C.c_int,
+        [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p],
+    ),
 }
 MULTI_QUANTILE_MAX_FRACTIONS = 32
+PCA_MAX_CHANNELS = 1024  # TIO_PCA_MAX_CHANNELS
 
 #: every symbol include/tio_hip.h declares for libtio_hip.so
 HIP_SYMBOLS = tuple("tio_" + n for n in (*PROTOTYPES, *HIP_ONLY_PROTOTYPES))

@@ -1551,6 +1551,61 @@ class Engine:
             table = cache[key] = h2d(host, device) if self.device_type == "cuda" else host
         return table
 
+    # -- PCA (transforms/intensity/pca.py) ---------------------------------------------------------------------------------
+    def _channel_matrix(self, data: Tensor, what: str) -> tuple[Tensor, int, int, int]:
+        """``data`` as the contiguous float32 ``(B, C, voxels)`` tensor the two PCA kernels read, with its three sizes."""
+        if data.ndim != 5:
+            raise ValueError(f"{what}: expected a (B, C, I, J, K) tensor, got {tuple(data.shape)}")
+        if data.dtype != torch.float32:
+            raise TypeError(f"{what}: float32 data only (the reference's `.float()` is the caller's), got {data.dtype}")
+        batch, channels = int(data.shape[0]), int(data.shape[1])
+        voxels = int(data.shape[2]) * int(data.shape[3]) * int(data.shape[4])
+        if not 1 <= channels <= _abi.PCA_MAX_CHANNELS or voxels < 1:
+            raise ValueError(f"{what}: 1 to {_abi.PCA_MAX_CHANNELS} channels of at least one voxel, got {tuple(data.shape)}")
+        if "channel_scatter" not in self._fn:
+            raise EngineError(f"{what}: the {self.name} engine has no PCA kernels")
+        return data.contiguous(), batch, channels, voxels
+
+    def channel_scatter(self, data: Tensor) -> tuple[Tensor, Tensor]:
+        """``(mean, scatter)`` of every batch element of a float32 ``(B, C, I, J, K)`` tensor over its voxels: the channel means
+        ``(B, C)`` and ``sum_v (x_v - mean)(x_v - mean)^T`` ``(B, C, C)``, float64 ON THE DEVICE, from one read of the data
+        (``tio_channel_scatter``).  Nothing is read back, nothing synchronises; two calls give the same bits."""
+        data, batch, channels, voxels = self._channel_matrix(data, "channel_scatter")
+        self._check("channel_scatter", data)
+        mean = torch.empty((batch, channels), dtype=torch.float64, device=data.device)
+        scatter = torch.empty((batch, channels, channels), dtype=torch.float64, device=data.device)
+        if batch == 0:
+            return mean, scatter
+        nbytes = int(self._fn["channel_scatter_workspace_bytes"](batch, channels, voxels))
+        if nbytes < 0:
+            raise EngineError("channel_scatter: " + (self._fn["last_error"]() or b"").decode(errors="replace"))
+        workspace = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=data.device)
+        self._call("channel_scatter", data, _ptr(data), batch, channels, voxels, _ptr(mean), _ptr(scatter), _ptr(workspace), nbytes,
+                   self._stream(data))
+        return mean, scatter
+
+    def channel_project(self, data: Tensor, center: Tensor, weights: Tensor, offset: Tensor, *, clip: bool) -> Tensor:
+        """``out[b, k] = sum_c weights[b, k, c] (data[b, c] - center[b, c]) + offset[b, k]`` per voxel, clamped to ``[0, 1]`` when
+        ``clip`` (a NaN stays NaN): float32 ``(B, q, I, J, K)`` from float32 ``(B, C, I, J, K)`` data and float32 device tensors
+        ``center (B, C)``, ``weights (B, q, C)``, ``offset (B, q)`` in one pass (``tio_channel_project``)."""
+        data, batch, channels, voxels = self._channel_matrix(data, "channel_project")
+        if weights.ndim != 3 or weights.shape[0] != batch or weights.shape[2] != channels or not 1 <= weights.shape[1] <= channels:
+            raise ValueError(f"channel_project: weights of shape {tuple(weights.shape)} for data of shape {tuple(data.shape)} (B, 1 .. C, C)")
+        components = int(weights.shape[1])
+        if tuple(center.shape) != (batch, channels) or tuple(offset.shape) != (batch, components):
+            raise ValueError(f"channel_project: center {tuple(center.shape)} and offset {tuple(offset.shape)} must be (B, C) and (B, q)")
+        for name, tensor in (("center", center), ("weights", weights), ("offset", offset)):
+            if tensor.dtype != torch.float32:
+                raise TypeError(f"channel_project: {name} must be float32, got {tensor.dtype}")
+        center, weights, offset = center.contiguous(), weights.contiguous(), offset.contiguous()
+        self._check("channel_project", data, center, weights, offset)
+        out = torch.empty((batch, components, *data.shape[2:]), dtype=torch.float32, device=data.device)
+        if batch == 0:
+            return out
+        self._call("channel_project", data, _ptr(data), batch, channels, voxels, _ptr(center), _ptr(weights), _ptr(offset), components,
+                   int(bool(clip)), _ptr(out), self._stream(data))
+        return out
+
     # -- feeding side -------------------------------------------------------
     def patch_accumulate(
         self,

@@ -37,6 +37,7 @@ from .orientation import Transpose
 from .pad import Crop
 from .pad import Pad
 from .parameter_range import Choice
+from .pca import PCA
 from .resize import Resize
 from .spatial import Affine
 from .spatial import ElasticDeformation
@@ -52,7 +53,7 @@ from .transform import Transform
 
 __all__ = [
     "Affine", "Anisotropy", "AppliedTransform", "BiasField", "Blur", "Choice", "Clamp", "Compose", "Contour", "CopyAffine", "Crop", "CropOrPad", "ElasticDeformation", "EnsureShapeMultiple", "Flip", "Gamma", "Ghosting",
-    "HistogramStandardization", "IntensityTransform", "KeepLargestComponent", "LabelsToImage", "Lambda", "Mask", "Motion", "Noise", "Normalize", "OneHot", "OneOf", "Pad", "RemapLabels", "RemoveLabels", "Reorient", "Resample", "RescaleIntensity",
+    "HistogramStandardization", "IntensityTransform", "KeepLargestComponent", "LabelsToImage", "Lambda", "Mask", "Motion", "Noise", "Normalize", "OneHot", "OneOf", "PCA", "Pad", "RemapLabels", "RemoveLabels", "Reorient", "Resample", "RescaleIntensity",
     "Resize", "SequentialLabels", "SomeOf", "Spatial", "SpatialTransform", "Spike", "Standardize", "Swap", "To", "ToReferenceSpace", "Transform", "Transpose", "ZNormalization",
     "apply_inverse_transform", "get_inverse_transform", "get_noise_rng", "set_noise_rng",
 ]
