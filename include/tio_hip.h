@@ -1011,6 +1011,45 @@ int tio_channel_project(const float* x, int32_t batch, int32_t channels, int64_t
                         void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* Points through a resampling (additive to ABI 18, HIP only)                */
+/* ------------------------------------------------------------------------ */
+/*
+ * A resampling computes out(o) = in(s(o)); a point attached to the image moves by s^-1.  One launch warps the points of a
+ * whole batch, one thread per point, 256-thread blocks none of which spans two elements (csrc/points.hip).
+ *   points / out        (n_total, 3) float32 on the device at any 4-byte boundary: input voxel coordinates (IJK) in, output
+ *                       voxel coordinates out; out may be points itself
+ *   status              (n_total,) int8 on the device or NULL: 0 converged (always, without a field), 1 not converged within
+ *                       TIO_POINTS_MAX_ITERATIONS steps (the best iterate is stored), 2 the element's block names control
+ *                       points outside the buffer (the affine-only answer is stored, the buffer is not read)
+ *   offsets_host / _dev the same batch + 1 int32 values on the host (validated: from 0 to n_total, never decreasing; sizes the
+ *                       grid) and on the device: element b owns the points offsets[b] .. offsets[b + 1] - 1; an element
+ *                       without points owns no block
+ *   blocks_dev          (batch, TIO_POINTS_BLOCK_DOUBLES) float64 on the device, 8-byte aligned; per element
+ *                         [0:12]  M, the 3x4 output-voxel -> input-voxel matrix inv(A_in) inv(T) A_out, row-major
+ *                         [12:24] its inverse, computed by the caller in float64
+ *                         [24:27] output shape   [27:30] input spacing   [30:33] output spacing   (mm)
+ *                         [33]    affine_first (0 / 1)
+ *                         [34:37] control grid (n_i, n_j, n_k)
+ *                         [37]    offset of this element's (n_i, n_j, n_k, 3) control points in control_points_dev, in floats;
+ *                                 -1: no field                          [38:40] reserved
+ *   control_points_dev  float32 on the device, control_floats of them (NULL / 0 when no element has a field)
+ * Without a field  o = Minv (p, 1).  With one, s(o) = p is solved for
+ *   affine_first:  s(o) = M o + d(o) / spacing_in          otherwise:  s(o) = M (o + d(o) / spacing_out)
+ * (spatial.py:1570-1577), d the trilinear interpolation of the control points at o_a (n_a - 1) / max(S_a - 1, 1), the index
+ * clamped to [0, n_a - 1] (align_corners=True, spatial.py:2171-2189; constant outside the output grid), by Newton's
+ * iteration from the affine-only answer with the cell's analytic Jacobian, the step halved while max|s(o) - p| does not
+ * decrease, until that residual is <= TIO_POINTS_TOLERANCE voxel.  That stop decides the status; a converged point then
+ * takes one more full step, kept when it lowers the residual.  All arithmetic is float64; the stored float32 is its one
+ * rounding.  Nothing is read back and nothing synchronises.  n_total > 2^31 - 1: TIO_ERR_INVALID_ARGUMENT.
+ */
+#define TIO_POINTS_BLOCK_DOUBLES 40
+#define TIO_POINTS_MAX_ITERATIONS 50
+#define TIO_POINTS_TOLERANCE 1.0e-7
+int tio_points_warp(const float* points, float* out, int8_t* status, int64_t n_total, const int32_t* offsets_host,
+                    const int32_t* offsets_dev, int32_t batch, const double* blocks_dev, const float* control_points_dev,
+                    int64_t control_floats, void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* Introspection                                                             */
 /* ------------------------------------------------------------------------ */
 int tio_abi_version(void);

@@ -29,6 +29,7 @@ DEFAULT_FILES = [
     "test_patches.py", "test_queue.py", "test_affine.py", "test_batch.py", "test_per_instance.py", "test_vectorization.py",
     "test_crop_or_pad.py", "test_ensure_shape_multiple.py", "test_to_reference_space.py", "test_copy_affine.py",
     "test_to.py", "test_lambda_transform.py",
+    "test_points.py", "test_bboxes.py", "test_axes.py", "test_image_annotations.py", "test_subject.py",
 ]
 
 

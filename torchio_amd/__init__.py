@@ -8,6 +8,9 @@ history/inverse behaviour; the compute under ``apply_transform`` runs as
 hand-written HIP kernels behind the C ABI of ``include/tio_hip.h``.
 """
 from .data import AffineMatrix
+from .data import BoundingBoxes
+from .data import BoundingBoxFormat
+from .data import Points
 from .data import GridSampler
 from .data import LabelSampler
 from .data import PatchAggregator
@@ -89,8 +92,8 @@ from .transforms import set_noise_rng
 __version__ = "0.1.0"
 
 __all__ = [
-    "Affine", "AffineMatrix", "Anisotropy", "AppliedTransform", "BiasField", "Blur", "Choice", "Clamp", "Compose", "Contour", "CopyAffine", "Crop", "CropOrPad", "ElasticDeformation", "EnsureShapeMultiple", "Flip",
+    "Affine", "AffineMatrix", "Anisotropy", "AppliedTransform", "BiasField", "Blur", "BoundingBoxFormat", "BoundingBoxes", "Choice", "Clamp", "Compose", "Contour", "CopyAffine", "Crop", "CropOrPad", "ElasticDeformation", "EnsureShapeMultiple", "Flip",
     "Gamma", "Ghosting", "GridSampler", "HistogramStandardization", "Image", "ImagesBatch", "ImagesLoader", "IntensityTransform", "KeepLargestComponent", "LabelMap", "LabelSampler", "LabelsToImage", "Lambda", "Mask", "Motion", "Noise", "Normalize", "OneHot", "OneOf",
-    "PCA", "Pad", "PatchAggregator", "PatchLocation", "PatchSampler", "Queue", "RemapLabels", "RemoveLabels", "Reorient", "Resample", "RescaleIntensity", "Resize", "ScalarImage", "SequentialLabels", "SomeOf", "Spatial", "SpatialTransform", "Spike", "Standardize", "Subject", "Swap",
+    "PCA", "Pad", "PatchAggregator", "PatchLocation", "PatchSampler", "Points", "Queue", "RemapLabels", "RemoveLabels", "Reorient", "Resample", "RescaleIntensity", "Resize", "ScalarImage", "SequentialLabels", "SomeOf", "Spatial", "SpatialTransform", "Spike", "Standardize", "Subject", "Swap",
     "SubjectsBatch", "SubjectsLoader", "To", "ToReferenceSpace", "Transform", "Transpose", "UniformSampler", "WeightedSampler", "ZNormalization", "apply_inverse_transform", "calibrate_draw_policy", "get_draw_policy", "set_draw_policy", "get_noise_plan", "set_noise_plan", "get_inverse_transform", "get_noise_rng", "get_resample_precision", "get_stencil_precision", "set_noise_rng", "set_resample_precision", "set_stencil_precision",
 ]

@@ -281,7 +281,13 @@ HIP_ONLY_PROTOTYPES = {
         C.c_int,
         [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p],
     ),
+    # Points through a resampling (additive to ABI 18): float32 points only, no CPU restatement either
+    "points_warp": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
+    ),
 }
+POINTS_BLOCK_DOUBLES = 40  # TIO_POINTS_BLOCK_DOUBLES
 MULTI_QUANTILE_MAX_FRACTIONS = 32
 PCA_MAX_CHANNELS = 1024  # TIO_PCA_MAX_CHANNELS
 

@@ -1,11 +1,14 @@
 from .affine import AffineMatrix
 from .aggregator import PatchAggregator
 from .batch import ImagesBatch
+from .bboxes import BoundingBoxes
+from .bboxes import BoundingBoxFormat
 from .batch import SubjectsBatch
 from .image import Image
 from .image import LabelMap
 from .image import ScalarImage
 from .patch import PatchLocation
+from .points import Points
 from .queue import Queue
 from .sampler import GridSampler
 from .sampler import LabelSampler
@@ -15,6 +18,6 @@ from .sampler import WeightedSampler
 from .subject import Subject
 
 __all__ = [
-    "AffineMatrix", "GridSampler", "Image", "ImagesBatch", "LabelMap", "LabelSampler", "PatchAggregator", "PatchLocation",
-    "PatchSampler", "Queue", "ScalarImage", "Subject", "SubjectsBatch", "UniformSampler", "WeightedSampler",
+    "AffineMatrix", "BoundingBoxFormat", "BoundingBoxes", "GridSampler", "Image", "ImagesBatch", "LabelMap", "LabelSampler", "PatchAggregator", "PatchLocation",
+    "PatchSampler", "Points", "Queue", "ScalarImage", "Subject", "SubjectsBatch", "UniformSampler", "WeightedSampler",
 ]

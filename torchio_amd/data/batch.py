@@ -57,13 +57,22 @@ class ImagesBatch(_History):
         self._affines = affines
         self._image_class = image_class
         self.applied_transforms = []
+        # image-level annotations, one {name: Points} / {name: BoundingBoxes} dict per element (point counts differ between
+        # elements: never stacked); None while no element carries any
+        self.points: list[dict] | None = None
+        self.bounding_boxes: list[dict] | None = None
 
     @classmethod
     def from_images(cls, images: list[Image]) -> "ImagesBatch":
         if not images:
             raise ValueError("Cannot create batch from empty list")
         data = torch.stack([image.data for image in images])
-        return cls(data, [image.affine.clone() for image in images], image_class=type(images[0]))
+        new = cls(data, [image.affine.clone() for image in images], image_class=type(images[0]))
+        if any(image.points for image in images):
+            new.points = [dict(image.points) for image in images]
+        if any(image.bounding_boxes for image in images):
+            new.bounding_boxes = [dict(image.bounding_boxes) for image in images]
+        return new
 
     @property
     def data(self) -> Tensor:
@@ -101,10 +110,16 @@ class ImagesBatch(_History):
 
     def to(self, *args, **kwargs) -> "ImagesBatch":
         self._data = self.data.to(*args, **kwargs)
+        _move_annotations((self.points, self.bounding_boxes), args, kwargs)
         return self
 
     def __getitem__(self, index: int) -> Image:
-        return self._image_class(self.data[index], affine=self._affines[index].clone())
+        annotations = {}
+        if self.points is not None:
+            annotations["points"] = dict(self.points[index])
+        if self.bounding_boxes is not None:
+            annotations["bounding_boxes"] = dict(self.bounding_boxes[index])
+        return self._image_class(self.data[index], affine=self._affines[index].clone(), **annotations)
 
     def __len__(self) -> int:
         return self.batch_size
@@ -118,6 +133,8 @@ class ImagesBatch(_History):
         new = ImagesBatch(data, [a.clone() for a in self._affines], image_class=self._image_class)
         if scope is not None:
             scope.borrow(new, data)  # cloned later unless a transform replaces it (see _lazy.py)
+        if self.points is not None or self.bounding_boxes is not None:
+            new.points, new.bounding_boxes = _copy.deepcopy(self.points, memo), _copy.deepcopy(self.bounding_boxes, memo)
         new.applied_transforms = list(self.applied_transforms)
         return new
 
@@ -134,6 +151,9 @@ class SubjectsBatch(_History):
         self._metadata = metadata or {}
         self.applied_transforms = []
         self._per_element_history: list[list[Any]] | None = None
+        # subject-level annotations, one dict per element like ImagesBatch's; None while no subject carries any
+        self.points: list[dict] | None = None
+        self.bounding_boxes: list[dict] | None = None
 
     @classmethod
     def from_subjects(cls, subjects: list[Any]) -> "SubjectsBatch":
@@ -145,7 +165,20 @@ class SubjectsBatch(_History):
             for name in first.images
         }
         metadata = {key: [subject.metadata[key] for subject in subjects] for key in first.metadata}
-        return cls(images, metadata=metadata)
+        new = cls(images, metadata=metadata)
+        if any(subject._points for subject in subjects):
+            new.points = [dict(subject._points) for subject in subjects]
+        if any(subject._bounding_boxes for subject in subjects):
+            new.bounding_boxes = [dict(subject._bounding_boxes) for subject in subjects]
+        return new
+
+    @property
+    def has_annotations(self) -> bool:
+        """Does any element carry points or boxes, at the subject or at an image?  (A batch without any takes none of the
+        annotation code paths of the spatial transforms.)"""
+        if self.points is not None or self.bounding_boxes is not None:
+            return True
+        return any(images.points is not None or images.bounding_boxes is not None for images in self._images.values())
 
     def adopt_history(self, source: "SubjectsBatch", subjects: list[Any]) -> None:
         """Carry the history of *source* over after its subjects were unbatched, processed and re-stacked (batch.py:269-284)."""
@@ -179,6 +212,7 @@ class SubjectsBatch(_History):
     def to(self, *args, **kwargs) -> "SubjectsBatch":
         for batch in self._images.values():
             batch.to(*args, **kwargs)
+        _move_annotations((self.points, self.bounding_boxes), args, kwargs)
         return self
 
     def __getitem__(self, key: str) -> ImagesBatch:
@@ -203,6 +237,9 @@ class SubjectsBatch(_History):
         for index in range(self.batch_size):
             entries: dict[str, Any] = {name: images[index] for name, images in self._images.items()}
             entries.update({key: values[index] for key, values in self._metadata.items()})
+            for annotations in (self.points, self.bounding_boxes):
+                if annotations is not None:
+                    entries.update(annotations[index])
             subject = Subject(**entries)
             history = _slice_history(self.applied_transforms, index)
             if self._per_element_history is not None:
@@ -234,6 +271,8 @@ class SubjectsBatch(_History):
             {name: _copy.deepcopy(images, memo) for name, images in self._images.items()},
             metadata=_copy.deepcopy(self._metadata, memo),
         )
+        if self.points is not None or self.bounding_boxes is not None:
+            new.points, new.bounding_boxes = _copy.deepcopy(self.points, memo), _copy.deepcopy(self.bounding_boxes, memo)
         new.applied_transforms = list(self.applied_transforms)
         if self._per_element_history is not None:
             new._per_element_history = [list(h) for h in self._per_element_history]
@@ -241,6 +280,13 @@ class SubjectsBatch(_History):
 
     def __repr__(self) -> str:
         return f"SubjectsBatch(batch_size={self.batch_size}, images=[{', '.join(self._images)}])"
+
+
+def _move_annotations(stores, args, kwargs) -> None:
+    for store in stores:
+        for element in store or ():
+            for annotation in element.values():
+                annotation.to(*args, **kwargs)
 
 
 def _slice_params(params: dict[str, Any], index: int, batched_keys: list[str]) -> dict[str, Any]:

@@ -13,12 +13,26 @@ import torch
 from torch import Tensor
 
 from .affine import AffineMatrix
+from .bboxes import BoundingBoxes
+from .points import Points
+
+
+def _parse_annotations(annotations, expected: type) -> dict:
+    """A shallow copy of a ``{name: Points}`` / ``{name: BoundingBoxes}`` dict (``None``: empty), every value checked."""
+    if annotations is None:
+        return {}
+    for key, value in annotations.items():
+        if not isinstance(value, expected):
+            raise TypeError(f"Expected {expected.__name__} for key {key!r}, got {type(value).__name__}")
+    return dict(annotations)
 
 
 class Image:
     """A 4-D ``(C, I, J, K)`` tensor plus its voxel-to-world affine."""
 
-    def __init__(self, data, *, affine=None, **metadata) -> None:
+    def __init__(self, data, *, affine=None, points=None, bounding_boxes=None, **metadata) -> None:
+        self._points = _parse_annotations(points, Points)
+        self._bounding_boxes = _parse_annotations(bounding_boxes, BoundingBoxes)
         if isinstance(data, np.ndarray):
             data = torch.as_tensor(data)
         if not isinstance(data, Tensor):
@@ -91,24 +105,54 @@ class Image:
         matrix = self._affine.data.clone()
         starts = [axis.indices(size)[0] for axis, size in zip((si, sj, sk), self.shape[1:], strict=True)]
         matrix[:3, 3] += matrix[:3, :3] @ torch.tensor(starts, dtype=torch.float64, device=matrix.device)
-        new = type(self)(cropped, affine=AffineMatrix(matrix), **_copy.deepcopy(self.metadata))
+        new = type(self)(cropped, affine=AffineMatrix(matrix), **self._copied_annotations(), **_copy.deepcopy(self.metadata))
         new.applied_transforms = list(self.applied_transforms)
         return new
 
+    # -- annotations ---------------------------------------------------------
+    @property
+    def points(self) -> dict[str, Points]:
+        """Named point sets attached to this image (image.py:524-526)."""
+        return self._points
+
+    @property
+    def bounding_boxes(self) -> dict[str, BoundingBoxes]:
+        """Named box sets attached to this image (image.py:529-531)."""
+        return self._bounding_boxes
+
+    def _copied_annotations(self, memo=None) -> dict:
+        return {
+            "points": {key: _copy.deepcopy(value, memo) for key, value in self._points.items()},
+            "bounding_boxes": {key: _copy.deepcopy(value, memo) for key, value in self._bounding_boxes.items()},
+        }
+
+    def new_like(self, *, data, affine=None) -> "Image":
+        """A new image of this class around *data*: metadata and annotations copied, this affine unless one is given
+        (image.py:670-697)."""
+        new_affine = self._affine.clone() if affine is None else (affine if isinstance(affine, AffineMatrix) else AffineMatrix(affine))
+        return type(self)(data, affine=new_affine, **self._copied_annotations(), **dict(self.metadata))
+
     def to(self, *args, **kwargs) -> "Image":
         self._data = self._data.to(*args, **kwargs)
+        for annotation in (*self._points.values(), *self._bounding_boxes.values()):
+            annotation.to(*args, **kwargs)
         return self
 
     def numpy(self) -> np.ndarray:
         return self._data.detach().cpu().numpy()
 
     def __deepcopy__(self, memo):
-        new = type(self)(self._data.clone(), affine=self._affine.clone(), **_copy.deepcopy(self.metadata, memo))
+        new = type(self)(self._data.clone(), affine=self._affine.clone(), **self._copied_annotations(memo), **_copy.deepcopy(self.metadata, memo))
         new.applied_transforms = list(self.applied_transforms)
         return new
 
     def __repr__(self) -> str:
-        return f"{type(self).__name__}(shape={self.shape}, dtype={self.dtype}, device={self.device})"
+        annotations = ""
+        if self._points:
+            annotations += f", points={{{', '.join(self._points)}}}"
+        if self._bounding_boxes:
+            annotations += f", bboxes={{{', '.join(self._bounding_boxes)}}}"
+        return f"{type(self).__name__}(shape={self.shape}, dtype={self.dtype}, device={self.device}{annotations})"
 
 
 def _normalize_index(item, ndim: int = 4) -> tuple[slice, ...]:

@@ -1606,6 +1606,53 @@ class Engine:
                    int(bool(clip)), _ptr(out), self._stream(data))
         return out
 
+    # -- annotations (data/points.py, data/bboxes.py) -------------------------------------------------------------------------
+    def warp_points(self, points: Tensor, offsets, blocks: Tensor, control_points: Tensor | None = None, *,
+                    return_status: bool = False):
+        """The points of a whole batch through ``s^-1`` of each element's resampling, in ONE launch (``tio_points_warp``).
+
+        ``points``: float32 ``(N, 3)`` on the device, input voxel coordinates (IJK), the elements' points one after the other;
+        ``offsets``: ``B + 1`` host integers, element ``b`` owns ``points[offsets[b]:offsets[b + 1]]`` (an empty element costs
+        nothing); ``blocks``: float64 ``(B, 40)``, one parameter block per element as ``include/tio_hip.h`` lays it out
+        (``transforms/_annotations.py: parameter_block``); ``control_points``: the float32 buffer the blocks' offsets point
+        into, or ``None`` when no element has a field.  Host ``blocks`` / ``control_points`` are uploaded with one staging copy.
+        Returns float32 ``(N, 3)`` output voxel coordinates, with ``return_status`` also the int8 ``(N,)`` solver status
+        (0 converged).  Nothing is read back and nothing synchronises.
+        """
+        if points.ndim != 2 or points.shape[1] != 3:
+            raise ValueError(f"warp_points: expected (N, 3) points, got {tuple(points.shape)}")
+        if points.dtype != torch.float32:
+            raise TypeError(f"warp_points: float32 points only, got {points.dtype}")
+        if "points_warp" not in self._fn:
+            raise EngineError(f"warp_points: the {self.name} engine has no tio_points_warp")
+        self._check("warp_points", points)
+        host_offsets = torch.as_tensor(offsets, device="cpu").to(torch.int32).contiguous().reshape(-1)
+        batch, total = host_offsets.numel() - 1, int(points.shape[0])
+        if batch < 0 or blocks.dtype != torch.float64 or tuple(blocks.shape) != (batch, _abi.POINTS_BLOCK_DOUBLES):
+            raise ValueError(
+                f"warp_points: {host_offsets.numel()} offsets need float64 blocks of shape ({batch}, {_abi.POINTS_BLOCK_DOUBLES}),"
+                f" got {blocks.dtype} {tuple(blocks.shape)}"
+            )
+        if control_points is not None and control_points.dtype != torch.float32:
+            raise TypeError(f"warp_points: float32 control points only, got {control_points.dtype}")
+        points = points.contiguous()
+        out = torch.empty((total, 3), dtype=torch.float32, device=points.device)
+        status = torch.empty((total,), dtype=torch.int8, device=points.device) if return_status else None
+        if batch > 0 and total > 0:
+            # one staging copy for whatever is still on the host; h2d_packed moves float32 words, so the int32 offsets and the
+            # float64 blocks travel as their own bits
+            field = None if control_points is None else control_points.contiguous().reshape(-1)
+            staged = [host_offsets.view(torch.float32), blocks.contiguous().reshape(-1), field]
+            if blocks.device.type == "cpu":
+                staged[1] = staged[1].view(torch.float32)
+            offsets_dev, blocks_dev, field = h2d_packed(staged, points.device)
+            self._check("warp_points", offsets_dev, blocks_dev, field)
+            self._call(
+                "points_warp", points, _ptr(points), _ptr(out), _ptr(status), total, _ptr(host_offsets), _ptr(offsets_dev), batch,
+                _ptr(blocks_dev), _ptr(field), 0 if field is None else field.numel(), self._stream(points),
+            )
+        return (out, status) if return_status else out
+
     # -- feeding side -------------------------------------------------------
     def patch_accumulate(
         self,

@@ -14,6 +14,7 @@ from typing import Any
 import torch
 
 from .. import ops
+from . import _annotations
 from ..data.batch import ImagesBatch
 from ..data.batch import SubjectsBatch
 from .transform import SpatialTransform
@@ -94,14 +95,20 @@ class Flip(SpatialTransform):
 
     def apply_transform(self, batch: SubjectsBatch, params: dict[str, Any]) -> SubjectsBatch:
         axes = params["axes"]
+        images = self._get_images(batch)
+        tracker = _annotations.track(batch, images)
         if self._is_per_instance_params(params):
-            for img_batch in self._get_images(batch).values():
+            for img_batch in images.values():
                 img_batch.data = _flip_per_element(img_batch.data, axes)
+            if tracker is not None:
+                tracker.finish(lambda name, index, in_shape, out_shape: _annotations.flip_matrix(axes[index], in_shape))
             return batch
         if not axes:
             return batch
-        for img_batch in self._get_images(batch).values():
+        for img_batch in images.values():
             img_batch.data = ops.engine().flip3d(img_batch.data, [int(a) for a in axes])
+        if tracker is not None:
+            tracker.finish(lambda name, index, in_shape, out_shape: _annotations.flip_matrix(axes, in_shape))
         return batch
 
     @property
@@ -133,6 +140,10 @@ class _FlipInverse(SpatialTransform):
         return {}
 
     def apply_transform(self, batch: SubjectsBatch, params: dict[str, Any]) -> SubjectsBatch:
-        for img_batch in self._get_images(batch).values():
+        images = self._get_images(batch)
+        tracker = _annotations.track(batch, images)
+        for img_batch in images.values():
             img_batch.data = _flip_per_element(img_batch.data, self._axes_per_element)
+        if tracker is not None:
+            tracker.finish(lambda name, index, in_shape, out_shape: _annotations.flip_matrix(self._axes_per_element[index], in_shape))
         return batch

@@ -19,6 +19,7 @@ import torch
 from torch import Tensor
 
 from .. import ops
+from . import _annotations
 from ..data.affine import AffineMatrix
 from ..data.affine import axcodes2ornt
 from ..data.affine import inv_ornt_aff
@@ -84,12 +85,18 @@ class Reorient(SpatialTransform):
         ornt = np.asarray(params["ornt"])
         if np.array_equal(ornt[:, 0], [0, 1, 2]) and np.all(ornt[:, 1] == 1):  # already there
             return batch
-        for img_batch in self._get_images(batch).values():
+        images = self._get_images(batch)
+        tracker = _annotations.track(batch, images)
+        for img_batch in images.values():
             original_shape = img_batch.data.shape[-3:]
             img_batch.data = _apply_reorientation(img_batch.data, ornt)
             inv_aff = inv_ornt_aff(ornt, original_shape)
             for affine in img_batch.affines:
                 affine._matrix.copy_(torch.as_tensor(affine.numpy() @ inv_aff, dtype=torch.float64))
+        if tracker is not None:  # the same permutation and flips as `_apply_reorientation` hands to the kernel
+            perm = [int(p) for p in np.argsort(ornt[:, 0])]
+            flips = [axis for axis in range(3) if ornt[axis, 1] == -1]
+            tracker.finish(lambda name, index, in_shape, out_shape: _annotations.permute_matrix(perm, flips, in_shape))
         return batch
 
     @property
@@ -113,12 +120,15 @@ class Transpose(SpatialTransform):
         return {}
 
     def apply_transform(self, batch: SubjectsBatch, params: dict[str, Any]) -> SubjectsBatch:
+        tracker = _annotations.track(batch, batch.images)
         for img_batch in batch.images.values():
             img_batch.data = ops.engine().permute3d(img_batch.data, (2, 1, 0))
             for affine in img_batch.affines:  # columns 0 and 2 trade places
                 m = affine._matrix.clone()
                 affine._matrix[:, 0] = m[:, 2]
                 affine._matrix[:, 2] = m[:, 0]
+        if tracker is not None:
+            tracker.finish(lambda name, index, in_shape, out_shape: _annotations.permute_matrix((2, 1, 0), (), in_shape))
         return batch
 
     @property
@@ -189,7 +199,8 @@ def _shifted_affine(image: Image, start) -> AffineMatrix:
 
 
 def _new_like(image: Image, data: Tensor, affine: AffineMatrix) -> Image:
-    return type(image)(data, affine=affine, **_copy.deepcopy(image.metadata))
+    # (the annotations ride along as they are; `_apply_per_image` moves them once all images stand on the new grid)
+    return type(image)(data, affine=affine, points=image.points, bounding_boxes=image.bounding_boxes, **_copy.deepcopy(image.metadata))
 
 
 def _pad_image(image: Image, padding, padding_mode: str, fill: float) -> Image:
@@ -261,17 +272,40 @@ class CropOrPad(SpatialTransform):
             images = {k: v for k, v in images.items() if k not in self.exclude}
         return images
 
+    def _grids_before(self, subject: Subject):
+        """The selected images' affines when the subject carries annotations (``None`` otherwise: nothing to move)."""
+        if not subject.all_points() and not subject.all_bounding_boxes():
+            return None
+        return {name: image.affine.clone() for name, image in self._selected(subject).items()}
+
+    @staticmethod
+    def _move_annotations(subject: Subject, before, start) -> None:
+        if not before:
+            return
+        maps = {
+            name: _annotations.GridMap(_annotations.shift_matrix(start), affine, subject._images[name].affine, subject._images[name].spatial_shape)
+            for name, affine in before.items()
+        }
+        device = next(iter(subject._images.values())).device
+        if device.type == "cpu" and ops.engine().device_type == "cuda" and torch.cuda.is_available():
+            device = torch.device("cuda", torch.cuda.current_device())  # staged through the engine's device, like `_pad_image`
+        _annotations.move_subject(subject, maps, device)
+
     def _apply_per_image(self, subject: Subject, padding, cropping) -> None:
         include = None if self.include is None else list(self.include)
         exclude = None if self.exclude is None else list(self.exclude)
         if padding is not None:
+            before = self._grids_before(subject)
             for name, image in self._selected(subject).items():
                 subject._images[name] = _pad_image(image, padding, self.padding_mode, self.fill)
+            self._move_annotations(subject, before, (-padding[0], -padding[2], -padding[4]))
             params = {"padding": padding, "padding_mode": self.padding_mode, "fill": self.fill}
             subject.applied_transforms.append(AppliedTransform(name="Pad", params=params, include=include, exclude=exclude))
         if cropping is not None:
+            before = self._grids_before(subject)
             for name, image in self._selected(subject).items():
                 subject._images[name] = _crop_image(image, cropping)
+            self._move_annotations(subject, before, (cropping[0], cropping[2], cropping[4]))
             subject.applied_transforms.append(AppliedTransform(name="Crop", params={"cropping": cropping}, include=include, exclude=exclude))
         params = {"padding": padding, "cropping": cropping}
         subject.applied_transforms.append(AppliedTransform(name="CropOrPad", params=params, include=include, exclude=exclude))
@@ -389,9 +423,13 @@ class ToReferenceSpace(SpatialTransform):
         return {}
 
     def apply_transform(self, batch: SubjectsBatch, params: dict[str, Any]) -> SubjectsBatch:
-        for img_batch in self._get_images(batch).values():
+        images = self._get_images(batch)
+        tracker = _annotations.track(batch, images)
+        for img_batch in images.values():
             new_affine = _reference_space_affine(self.reference, tuple(int(s) for s in img_batch.data.shape[2:]))
             img_batch.affines[:] = [new_affine.clone() for _ in img_batch.affines]
+        if tracker is not None:  # the voxels stay: IJK coordinates keep their values, anatomical ones follow the new affine
+            tracker.finish(lambda name, index, in_shape, out_shape: np.eye(4))
         return batch
 
     @staticmethod
@@ -415,9 +453,14 @@ class CopyAffine(SpatialTransform):
         if self.target not in batch.images:
             raise KeyError(f"Reference image '{self.target}' not found. Available: {list(batch.images.keys())}")
         ref_affines = batch.images[self.target].affines
+        # the voxels stay, so the annotations stay ON their voxels: IJK coordinates keep their values
+        # and adopt the new affine, anatomical ones are re-expressed through it
+        tracker = _annotations.track(batch, batch.images)
         for name, img_batch in batch.images.items():
             if name == self.target:
                 continue
             for i, affine in enumerate(img_batch.affines):
                 affine._matrix.copy_(ref_affines[i]._matrix)
+        if tracker is not None:
+            tracker.finish(lambda name, index, in_shape, out_shape: None if name == self.target else np.eye(4))
         return batch

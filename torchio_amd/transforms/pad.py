@@ -15,6 +15,7 @@ import torch
 from torch import Tensor
 
 from .. import ops
+from . import _annotations
 from ..data.batch import SubjectsBatch
 from .transform import SpatialTransform
 
@@ -101,10 +102,14 @@ class Pad(SpatialTransform):
 
     def apply_transform(self, batch: SubjectsBatch, params: dict[str, Any]) -> SubjectsBatch:
         i0, i1, j0, j1, k0, k1 = params["padding"]
-        for img_batch in self._get_images(batch).values():
+        images = self._get_images(batch)
+        tracker = _annotations.track(batch, images)
+        for img_batch in images.values():
             img_batch.data = pad_tensor(img_batch.data, (i0, i1, j0, j1, k0, k1), params["padding_mode"], params["fill"])
             for affine in img_batch.affines:  # the origin moves back by the leading pad
                 affine._matrix[:3, 3] += affine.data[:3, :3] @ affine.data.new_tensor([-float(i0), -float(j0), -float(k0)])
+        if tracker is not None:
+            tracker.finish(lambda name, index, in_shape, out_shape: _annotations.shift_matrix((-i0, -j0, -k0)))
         return batch
 
     @property
@@ -127,12 +132,16 @@ class Crop(SpatialTransform):
 
     def apply_transform(self, batch: SubjectsBatch, params: dict[str, Any]) -> SubjectsBatch:
         i0, i1, j0, j1, k0, k1 = params["cropping"]
-        for img_batch in self._get_images(batch).values():
+        images = self._get_images(batch)
+        tracker = _annotations.track(batch, images)
+        for img_batch in images.values():
             data = img_batch.data
             si, sj, sk = data.shape[-3:]
             img_batch.data = data[..., i0 : si - i1 or None, j0 : sj - j1 or None, k0 : sk - k1 or None]
             for affine in img_batch.affines:
                 affine._matrix[:3, 3] += affine.data[:3, :3] @ affine.data.new_tensor([float(i0), float(j0), float(k0)])
+        if tracker is not None:
+            tracker.finish(lambda name, index, in_shape, out_shape: _annotations.shift_matrix((i0, j0, k0)))
         return batch
 
     @property

@@ -10,6 +10,7 @@ from __future__ import annotations
 from typing import Any
 
 from .. import ops
+from . import _annotations
 from ..data.batch import SubjectsBatch
 from ..data.image import LabelMap
 from .transform import SpatialTransform
@@ -32,12 +33,17 @@ class Resize(SpatialTransform):
     def apply_transform(self, batch: SubjectsBatch, params: dict[str, Any]) -> SubjectsBatch:
         target = [int(s) for s in params["target_shape"]]
         engine = ops.engine()
-        for img_batch in batch.images.values():
+        tracker = _annotations.track(batch, batch.images)
+        nearest = {}
+        for name, img_batch in batch.images.items():
             is_label = issubclass(img_batch._image_class, LabelMap)
             mode = self.label_interpolation if is_label else self.image_interpolation
+            nearest[name] = mode == "nearest"
             old_shape = tuple(img_batch.data.shape[2:])
             img_batch.data = engine.interpolate3d(img_batch.data, target, "nearest" if mode == "nearest" else "linear")
             for affine in img_batch.affines:  # spacing changes to fit the new shape into the same field of view
                 for axis in range(3):
                     affine._matrix[:3, axis] *= old_shape[axis] / target[axis]
+        if tracker is not None:  # annotations follow the interpolation's own source coordinates
+            tracker.finish(lambda name, index, in_shape, out_shape: _annotations.resize_matrix(in_shape, out_shape, nearest=nearest[name]))
         return batch

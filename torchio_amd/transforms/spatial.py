@@ -43,6 +43,7 @@ from .blur import _stacked_gaussian_taps
 from .parameter_range import Choice
 from .parameter_range import ScalarDrawPlan
 from .parameter_range import _ParameterRange
+from . import _annotations
 from ._lazy_params import LazyParams
 from .transform import SpatialTransform
 
@@ -426,6 +427,7 @@ class Spatial(SpatialTransform):
                 ahead.join(tensor.device)
                 prepared = ahead.payload
         target_space = _deserialize_space(params["target"])
+        in_grid = _grid_of(batch.images[selected[0]]) if batch.has_annotations else None
         if prepared is not None:  # (the parameters were resolved by `_prefetch`, which only prepares launches that sample)
             matrix = field = displacement = per_sample = None
         else:
@@ -449,6 +451,10 @@ class Spatial(SpatialTransform):
             per_sample=per_sample,
             prepared=prepared,
         )
+        if in_grid is not None:
+            if prepared is not None:  # (the image launch took the drawn-ahead geometry: the annotations read the parameters themselves)
+                matrix, field, _, per_sample = _resolve_spatial_params(params)
+            _move_spatial_annotations(batch, selected, in_grid, target_space, matrix, field, per_sample, params["affine_first"])
         return batch
 
     @property
@@ -523,9 +529,11 @@ class _SpatialInverse(SpatialTransform):
         displacement = None
         if self.per_sample is None and self.control_points is not None:
             displacement = _max_abs_displacement(self.control_points)
+        image_names = list(self._get_images(batch))
+        in_grid = _grid_of(batch.images[image_names[0]]) if image_names and batch.has_annotations else None
         _apply_spatial_to_batch(
             batch=batch,
-            image_names=list(self._get_images(batch)),
+            image_names=image_names,
             target_space=self.target,
             affine_matrix=self.affine_matrix,
             control_points=self.control_points,
@@ -539,7 +547,38 @@ class _SpatialInverse(SpatialTransform):
             default_pad_label=self.default_pad_label,
             per_sample=self.per_sample,
         )
+        if in_grid is not None:
+            _move_spatial_annotations(batch, image_names, in_grid, self.target, self.affine_matrix, self.control_points, self.per_sample, self.affine_first)
         return batch
+
+
+def _grid_of(first: ImagesBatch):
+    """``(shape, affine)`` of the grid a launch reads: the first selected image's first element (`_prepare_launch_geometry`)."""
+    return tuple(int(s) for s in first._data.shape[2:]), first.affines[0]
+
+
+def _move_spatial_annotations(batch: SubjectsBatch, image_names, in_grid, target_space, affine_matrix, control_points, per_sample, affine_first) -> None:
+    """Points and boxes follow the launch of `_apply_spatial_to_batch`: per element the same float64
+    product ``inv(A_in) inv(T) A_out`` the launch casts to float32, and the element's own control points."""
+    _, in_affine = in_grid
+    out_shape, out_affine = target_space if target_space is not None else in_grid
+    batch_size = batch.images[image_names[0]].batch_size
+    if per_sample is None:
+        matrices, fields = [affine_matrix] * batch_size, [control_points] * batch_size
+    else:
+        matrices, fields = per_sample.affine_matrices, per_sample.control_points
+        if isinstance(fields, _StackedFields):
+            fields = list(fields.stacked.unbind(0))
+    in_inverse = in_affine.inverse_numpy() if hasattr(in_affine, "inverse_numpy") else np.linalg.inv(in_affine.numpy())
+    out_matrix = out_affine.numpy()
+    grids = []
+    for matrix, field in zip(matrices, fields, strict=True):
+        if per_sample is not None and target_space is None and matrix is None and field is None:
+            grids.append(None)  # a gated-out element: passed through, its annotations stay
+            continue
+        world = np.eye(4) if matrix is None else np.linalg.inv(np.asarray(matrix, dtype=np.float64))
+        grids.append(_annotations.GridMap((in_inverse @ world) @ out_matrix, in_affine, out_affine, out_shape, field=field, affine_first=affine_first))
+    _annotations.move_batch(batch, {name: grids for name in image_names})
 
 
 class Resample(Spatial):
