@@ -1050,6 +1050,64 @@ int tio_points_warp(const float* points, float* out, int8_t* status, int64_t n_t
                     int64_t control_floats, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* Patch feeding: weighted centres and patch batches (additive to ABI 18, HIP only) */
+/* ------------------------------------------------------------------------ */
+/*
+ * WeightedSampler / LabelSampler of the reference (data/sampler.py:252-274, 320-360) draw a patch CENTRE from a probability
+ * map whose border is masked (a patch centred there would stick out: half <= pos < shape - half on every axis, half =
+ * patch / 2 > 0), one torch.multinomial over the whole volume per patch.  Here the law is a two-level inverse CDF.
+ *
+ * The weight source is channel 0 of an image, (I, J, K) dense, of any tio_dtype (element_type):
+ *   label_mode 0   the voxel converted to float32 (`.float()`, sampler.py:281);
+ *   label_mode 1   a label looked up in the HOST table of n_labels <= TIO_CENTRE_MAX_LABELS (label_values[q],
+ *                  label_weights[q]) pairs, later pairs overriding earlier ones (the loop of assignments at sampler.py:324-327),
+ *                  0 for a label the table does not hold; n_labels == 0: weight = label > 0 (sampler.py:329).
+ * A SEGMENT is TIO_CENTRE_SEGMENT consecutive flat voxels (the last one may be shorter).
+ *
+ * tio_centre_law_sums: prefix_dev receives ceil(I J K / TIO_CENTRE_SEGMENT) float64 values, the inclusive prefix sums of the
+ * segments' masked weights; record_dev the total and whether any unmasked weight is negative, infinite or NaN.  The masked
+ * map is never stored.  Three stream-ordered steps: the record is cleared; one launch adds every segment in a fixed order
+ * within the block that owns it; one single-block launch adds the segment totals in ascending order.  No floating-point
+ * atomic: the values do not depend on the launch geometry.
+ *
+ * tio_centre_draw: n_draws independent draws with replacement from the law the same source arguments describe, prefix_dev /
+ * record_dev as left by tio_centre_law_sums.  Uniforms: uniforms_dev[n] (float64 in [0, 1)) or, when that is NULL, this
+ * library's stream: philox4x32_10 (csrc/philox_normal.hpp), counter {n lo, n hi, 2, 0}, key {seed lo, seed hi},
+ * u = ((c[0] >> 5) * 2^26 + (c[1] >> 6)) * 2^-53 (stream ids 0 and 1 of that counter word belong to the noise).
+ * uniforms_out_dev (or NULL) receives the values used.  Per draw: t = u * total; the first segment whose prefix exceeds t
+ * (binary search); its weights recomputed as the sums computed them; the first voxel of positive weight at which the running
+ * float64 sum, added in flat order, exceeds t - prefix_before; if rounding leaves none, the segment's last voxel of positive
+ * weight.  centres_dev[n]: the flat index (-1 when the law holds no positive weight); corners_dev[n][3]:
+ * min(max(centre - patch / 2, 0), shape - patch).  A voxel of zero weight is never chosen.
+ */
+#define TIO_CENTRE_SEGMENT 2048
+#define TIO_CENTRE_MAX_LABELS 64
+typedef struct tio_centre_record {
+  double total;     /* float64 sum of the masked weights */
+  int32_t invalid;  /* 1: an unmasked weight is negative, infinite or NaN */
+  int32_t reserved; /* 0 */
+} tio_centre_record;
+int tio_centre_law_sums(const void* weights, int32_t element_type, int32_t label_mode, const double* label_values,
+                        const float* label_weights, int32_t n_labels, const int32_t shape[3], const int32_t patch[3],
+                        double* prefix_dev, tio_centre_record* record_dev, void* stream);
+int tio_centre_draw(const void* weights, int32_t element_type, int32_t label_mode, const double* label_values,
+                    const float* label_weights, int32_t n_labels, const int32_t shape[3], const int32_t patch[3],
+                    const double* prefix_dev, const tio_centre_record* record_dev, int64_t n_draws, uint64_t seed,
+                    const double* uniforms_dev, double* uniforms_out_dev, int64_t* centres_dev, int32_t* corners_dev, void* stream);
+
+/*
+ * All patches of one image in one launch (the slicing of sampler.py:54-67, N times, and the torch.stack of the collation):
+ * x (channels, I, J, K) -> y (n_patches, channels, pi, pj, pk), elements of 1, 2, 4 or 8 bytes moved as bits.  corners_dev is
+ * int32 [n_patches][3] ON THE DEVICE (after tio_centre_draw nothing goes through the host); each corner is clamped to
+ * [0, shape - patch] inside the kernel, so no read leaves x whatever the array holds.  y is written in aligned 16-byte
+ * stores (single elements up to its first and after its last 16-byte boundary of each patch volume), x is read with the
+ * widest loads the address of each 16-byte group allows.  patch > shape on any axis: TIO_ERR_INVALID_ARGUMENT, nothing
+ * launched.
+ */
+int tio_patch_gather(const void* x, void* y, int32_t element_bytes, int32_t channels, const int32_t shape[3], const int32_t patch[3],
+                     const int32_t* corners_dev, int32_t n_patches, void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* Introspection                                                             */
 /* ------------------------------------------------------------------------ */
 int tio_abi_version(void);

@@ -286,7 +286,22 @@ HIP_ONLY_PROTOTYPES = {
         C.c_int,
         [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
     ),
+    # Patch feeding: weighted centre draws and the patch gather (additive to ABI 18): no CPU restatement either
+    "centre_law_sums": (
+        C.c_int,
+        [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_float), C.c_int32, _I32x3, _I32x3, C.c_void_p, C.c_void_p,
+         C.c_void_p],
+    ),
+    "centre_draw": (
+        C.c_int,
+        [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_float), C.c_int32, _I32x3, _I32x3, C.c_void_p, C.c_void_p,
+         C.c_int64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "patch_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _I32x3, _I32x3, C.c_void_p, C.c_int32, C.c_void_p]),
 }
+CENTRE_SEGMENT = 2048  # TIO_CENTRE_SEGMENT
+CENTRE_MAX_LABELS = 64  # TIO_CENTRE_MAX_LABELS
+CENTRE_RECORD_BYTES = 16  # sizeof(tio_centre_record): float64 total, int32 invalid, int32 reserved
 POINTS_BLOCK_DOUBLES = 40  # TIO_POINTS_BLOCK_DOUBLES
 MULTI_QUANTILE_MAX_FRACTIONS = 32
 PCA_MAX_CHANNELS = 1024  # TIO_PCA_MAX_CHANNELS

@@ -15,9 +15,11 @@ from .sampler import LabelSampler
 from .sampler import PatchSampler
 from .sampler import UniformSampler
 from .sampler import WeightedSampler
+from .sampler import get_centre_draw
+from .sampler import set_centre_draw
 from .subject import Subject
 
 __all__ = [
     "AffineMatrix", "BoundingBoxFormat", "BoundingBoxes", "GridSampler", "Image", "ImagesBatch", "LabelMap", "LabelSampler", "PatchAggregator", "PatchLocation",
-    "PatchSampler", "Points", "Queue", "ScalarImage", "Subject", "SubjectsBatch", "UniformSampler", "WeightedSampler",
+    "PatchSampler", "Points", "Queue", "ScalarImage", "Subject", "SubjectsBatch", "UniformSampler", "WeightedSampler", "get_centre_draw", "set_centre_draw",
 ]

@@ -63,10 +63,13 @@ class ImagesBatch(_History):
         self.bounding_boxes: list[dict] | None = None
 
     @classmethod
-    def from_images(cls, images: list[Image]) -> "ImagesBatch":
+    def from_images(cls, images: list[Image], *, data: Tensor | None = None) -> "ImagesBatch":
+        """*data*: the stacked voxels where somebody has them already (``PatchSampler.sample_batch``: one gather launch);
+        affines and annotations still come from *images*."""
         if not images:
             raise ValueError("Cannot create batch from empty list")
-        data = torch.stack([image.data for image in images])
+        if data is None:
+            data = torch.stack([image.data for image in images])
         new = cls(data, [image.affine.clone() for image in images], image_class=type(images[0]))
         if any(image.points for image in images):
             new.points = [dict(image.points) for image in images]
@@ -156,12 +159,13 @@ class SubjectsBatch(_History):
         self.bounding_boxes: list[dict] | None = None
 
     @classmethod
-    def from_subjects(cls, subjects: list[Any]) -> "SubjectsBatch":
+    def from_subjects(cls, subjects: list[Any], *, data: dict[str, Tensor] | None = None) -> "SubjectsBatch":
+        """*data*: already stacked ``(B, C, I, J, K)`` voxels per image name (see ``ImagesBatch.from_images``)."""
         if not subjects:
             raise ValueError("Cannot create batch from empty list")
         first = subjects[0]
         images = {
-            name: ImagesBatch.from_images([subject.images[name] for subject in subjects])
+            name: ImagesBatch.from_images([subject.images[name] for subject in subjects], data=None if data is None else data.get(name))
             for name in first.images
         }
         metadata = {key: [subject.metadata[key] for subject in subjects] for key in first.metadata}

@@ -59,6 +59,9 @@ class Queue(IterableDataset):
         transform: applied to every subject before its patches are cut.
         subject_sampler: a ``torch.utils.data.Sampler`` of subject indices (``DistributedSampler`` = the multi-GPU
             split of the feeding side, reference queue.py:48-50); excludes ``shuffle_subjects``.
+        gather_patches: take a subject's patches from ``patch_sampler.sample_batch(subject, patches_per_volume)`` — on a
+            GPU-resident subject one gather launch per image — and unbatch them into the buffer, which then holds copies
+            and no longer keeps every transformed parent volume alive.  Default: views of the parent, as the reference.
     """
 
     def __init__(
@@ -72,6 +75,7 @@ class Queue(IterableDataset):
         shuffle_patches: bool = True,
         transform: Any | None = None,
         subject_sampler: Sampler | None = None,
+        gather_patches: bool = False,
     ) -> None:
         if subject_sampler is not None and shuffle_subjects:
             raise ValueError("shuffle_subjects must be False when subject_sampler is provided (the sampler controls the order)")
@@ -84,6 +88,7 @@ class Queue(IterableDataset):
         self.shuffle_patches = shuffle_patches
         self.transform = transform
         self.subject_sampler = subject_sampler
+        self.gather_patches = gather_patches
 
     # ---- the pipeline ----------------------------------------------------------------------
     def _subject_order(self) -> list[Subject]:
@@ -99,6 +104,8 @@ class Queue(IterableDataset):
         return subject if self.transform is None else self.transform(subject)
 
     def _patches_of(self, subject: Subject) -> list[Subject]:
+        if self.gather_patches:
+            return self.patch_sampler.sample_batch(subject, self.patches_per_volume).unbatch()
         return list(itertools.islice(self.patch_sampler(subject), self.patches_per_volume))
 
     def _hand_out(self, buffer: list[Subject]) -> Iterator[Subject]:

@@ -13,6 +13,11 @@ pieces:
 * :class:`CentreLaw` — a discrete distribution over patch CENTRES (probability map or label weights) with
   the voxels whose patch would stick out of the volume masked by broadcasting three 1-D masks.
 
+Beyond the reference: :meth:`PatchSampler.sample_batch` / :meth:`GridSampler.batches` hand out a whole batch of patches — the
+collation of as many cut patches, each image's voxels from one ``Engine.patch_gather`` launch (:func:`gather_batch`) — and
+:func:`set_centre_draw` lets the weighted samplers draw a batch's centres on the device (``Engine.centre_draw``; opt-in, the
+reference's host draw stays the default and iteration never changes).
+
 ``GridSampler`` pairs with :class:`~torchio_amd.data.aggregator.PatchAggregator`.
 """
 from __future__ import annotations
@@ -26,6 +31,7 @@ from torch import Tensor
 from torch.utils.data import Dataset
 from torch.utils.data import IterableDataset
 
+from .batch import SubjectsBatch
 from .patch import PatchLocation
 from .subject import Subject
 
@@ -92,6 +98,53 @@ class CentreLaw:
         return (i, j, k)
 
 
+_CENTRE_DRAW = "reference"
+
+
+def set_centre_draw(mode: str) -> None:
+    """Where ``WeightedSampler.sample_batch`` / ``LabelSampler.sample_batch`` draw their patch centres.
+
+    ``"reference"`` (default): one ``torch.multinomial`` on the host per patch, consuming the global CPU generator exactly
+    as the reference does.  ``"device"``: one ``Engine.centre_draw`` per call from the package's own Philox stream (stream
+    id 2), seeded with ONE ``torch.randint(0, 2**62, (1,))`` from the global CPU generator — reproducible under
+    ``torch.manual_seed``, but other centres than the reference's and another consumption of the generator.  Iterating a
+    sampler is the reference's road in both modes.
+    """
+    global _CENTRE_DRAW
+    if mode not in ("reference", "device"):
+        raise ValueError(f"centre draw mode must be 'reference' or 'device', got {mode!r}")
+    _CENTRE_DRAW = mode
+
+
+def get_centre_draw() -> str:
+    return _CENTRE_DRAW
+
+
+def gather_batch(subject: Subject, locations: list[PatchLocation], corners_dev: Tensor | None = None) -> SubjectsBatch:
+    """``SubjectsBatch.from_subjects([cut(subject, where) for where in locations])``, each image's voxels from ONE
+    ``Engine.patch_gather`` launch where the subject lives on the GPU.  Affines, annotations and metadata are those of the
+    slicing road; a host-resident subject, a non-contiguous image and a patch that does not fit take that road for the voxels
+    too.  *corners_dev*: the corners as a device draw left them (int32 ``(N, 3)``), else they go up in one staged copy."""
+    patches = [cut(subject, where) for where in locations]
+    if not patches:
+        raise ValueError("Cannot create batch from empty list")
+    size = locations[0].size
+    images = list(subject.images.values())
+    fits = all(where.size == size for where in locations) and all(
+        image.data.device.type == "cuda" and image.data.is_contiguous() and all(p <= s for p, s in zip(size, image.data.shape[1:], strict=True))
+        for image in images
+    )
+    if not fits or not images or any(image.data.device != images[0].data.device for image in images):
+        return SubjectsBatch.from_subjects(patches)
+    from ..ops import engine  # noqa: PLC0415
+    from ..ops import h2d  # noqa: PLC0415
+
+    if corners_dev is None:  # one small copy through the pinned staging ring
+        corners_dev = h2d(torch.tensor([where.index for where in locations], dtype=torch.int32).reshape(-1, 3), images[0].data.device)
+    data = {name: engine().patch_gather(image.data, corners_dev, size) for name, image in subject.images.items()}
+    return SubjectsBatch.from_subjects(patches, data=data)
+
+
 class PatchSampler:
     """Common part: the patch size and the cutting (reference sampler.py:24-72)."""
 
@@ -103,6 +156,10 @@ class PatchSampler:
 
     def _extract_patch(self, subject: Subject, location: PatchLocation) -> Subject:
         return cut(subject, location)
+
+    def sample_batch(self, subject: Subject, num_patches: int) -> SubjectsBatch:
+        """``num_patches`` patches of *subject* as one batch: the collation of as many patches of ``self(subject)``."""
+        raise NotImplementedError(f"{type(self).__name__} must implement sample_batch")
 
 
 class GridSampler(PatchSampler, Dataset):
@@ -129,6 +186,14 @@ class GridSampler(PatchSampler, Dataset):
     def __getitem__(self, index: int) -> Subject:
         return cut(self.subject, self.locations[index])
 
+    def batches(self, batch_size: int) -> Iterator[SubjectsBatch]:
+        """The grid in ``locations`` order, ``batch_size`` patches at a time (the last batch may be shorter): what collating
+        consecutive items yields, with one gather launch per image and batch."""
+        if batch_size < 1:
+            raise ValueError(f"batch_size must be at least 1, got {batch_size}")
+        for start in range(0, len(self.locations), batch_size):
+            yield gather_batch(self.subject, self.locations[start : start + batch_size])
+
 
 class _RandomSampler(PatchSampler, IterableDataset):
     """Iterable samplers: an endless (or ``num_patches`` long) stream of patches of one subject."""
@@ -149,6 +214,14 @@ class _RandomSampler(PatchSampler, IterableDataset):
 
     def _corners(self, subject: Subject) -> Iterator[Triple]:
         raise NotImplementedError
+
+    def _batch_corners(self, subject: Subject, num_patches: int) -> tuple[list[Triple], Tensor | None]:
+        """The corners of one batch on the host and, where a device draw made them, on the device as well."""
+        return list(itertools.islice(self._corners(subject), num_patches)), None
+
+    def sample_batch(self, subject: Subject, num_patches: int) -> SubjectsBatch:
+        corners, corners_dev = self._batch_corners(subject, int(num_patches))
+        return gather_batch(subject, [PatchLocation(index=corner, size=self.patch_size) for corner in corners], corners_dev)
 
 
 class UniformSampler(_RandomSampler):
@@ -186,6 +259,33 @@ class WeightedSampler(_RandomSampler):
         while True:
             yield corner_of(law.centre(int(torch.multinomial(flat, 1).item())), shape, self.patch_size)
 
+    def _draw_source(self, subject: Subject) -> tuple[Tensor, list[tuple[float, float]] | None]:
+        """What the device draw reads: the weight source ``(I, J, K)`` and, for labels, the table to look them up in."""
+        from ..ops import _DTYPE_CODES  # noqa: PLC0415
+
+        data = subject.images[self.probability_map].data
+        return (data[0], None) if data.dtype in _DTYPE_CODES else (self._weights(subject), None)
+
+    def _batch_corners(self, subject: Subject, num_patches: int) -> tuple[list[Triple], Tensor | None]:
+        if get_centre_draw() != "device":
+            return super()._batch_corners(subject, num_patches)
+        from ..ops import engine  # noqa: PLC0415
+
+        source, table = self._draw_source(subject)
+        if source.device.type != "cuda":
+            raise RuntimeError(
+                f"set_centre_draw('device') draws on the GPU, but '{self.probability_map}' lives on {source.device}: move the subject"
+                " there (`subject.to('cuda')`) or go back to set_centre_draw('reference')"
+            )
+        seed = int(torch.randint(0, 2**62, (1,)).item())  # the one consumption of the global CPU generator per call
+        draw = engine().centre_draw(source, self.patch_size, num_patches, label_table=table, seed=seed)
+        corners, total, invalid = draw.on_host()
+        if invalid:
+            raise RuntimeError("probability tensor contains either `inf`, `nan` or element < 0")
+        if total == 0:
+            raise RuntimeError(f"Probability map '{self.probability_map}' is all zeros")
+        return [tuple(corner) for corner in corners.tolist()], draw.corners  # type: ignore[misc]
+
 
 class LabelSampler(WeightedSampler):
     """Centres on labelled voxels, optionally weighted per label (reference sampler.py:313-366)."""
@@ -204,3 +304,17 @@ class LabelSampler(WeightedSampler):
         for label, weight in self.label_probabilities.items():
             weights = torch.where(labels == label, torch.full((), float(weight), device=labels.device), weights)
         return weights
+
+    def _draw_source(self, subject: Subject) -> tuple[Tensor, list[tuple[float, float]] | None]:
+        from .. import _abi  # noqa: PLC0415
+        from ..ops import _DTYPE_CODES  # noqa: PLC0415
+
+        labels = subject.images[self.label_name].data[0]
+        table = self.label_probabilities
+        if table is None:
+            return (labels, []) if labels.dtype in _DTYPE_CODES else (self._weights(subject), None)  # an empty table: label > 0
+        if labels.dtype not in _DTYPE_CODES or not 0 < len(table) <= _abi.CENTRE_MAX_LABELS:
+            return self._weights(subject), None  # the weight tensor of the reference road, handed over in map mode
+        # `labels == label` compares in the labels' own type when that is a floating-point one: the key is rounded to it
+        rounded = (lambda key: float(torch.tensor(float(key), dtype=labels.dtype))) if labels.dtype.is_floating_point else float
+        return labels, [(rounded(label), float(weight)) for label, weight in table.items()]

@@ -14,6 +14,7 @@ import math
 import os
 import threading
 from collections.abc import Sequence
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -1696,6 +1697,96 @@ class Engine:
                 _i32x3(out.shape[1:]), _ptr(chunk), chunk.shape[0], _i32x3(chunk.shape[2:]), table, code,
                 _ptr(window_tensors[0]), _ptr(window_tensors[1]), _ptr(window_tensors[2]), self._stream(out),
             )
+
+
+    def centre_draw(self, source: Tensor, patch_size: Sequence[int], num_draws: int, *, label_table: Sequence[tuple[float, float]] | None = None,
+                    seed: int = 0, uniforms: Tensor | None = None, return_uniforms: bool = False) -> "CentreDraw":
+        """``num_draws`` patch centres drawn with replacement from the border-masked law of ``source`` ``(I, J, K)``
+        (``tio_centre_law_sums`` + ``tio_centre_draw``: three launches, nothing read back, nothing synchronises).
+
+        ``label_table is None``: ``source`` holds the weights, any engine dtype, each voxel converted to float32.  Otherwise
+        ``source`` holds labels and the table at most 64 ``(label value, weight)`` pairs, later pairs overriding earlier ones;
+        an empty table means ``weight = label > 0``.  ``uniforms``: float64 ``(num_draws,)`` in ``[0, 1)`` on the device, or
+        ``None`` for the package's Philox stream under ``seed``.  The result's ``corners`` and ``record`` are views of one int32
+        tensor ``packed``, so one ``packed.cpu()`` brings both to the host.
+        """
+        if source.ndim != 3:
+            raise ValueError(f"centre_draw: expected an (I, J, K) weight source, got {tuple(source.shape)}")
+        patch = [int(p) for p in patch_size]
+        if len(patch) != 3 or any(p < 1 for p in patch):
+            raise ValueError(f"centre_draw: patch_size must be three positive integers, got {tuple(patch_size)}")
+        num_draws = int(num_draws)
+        if num_draws < 0:
+            raise ValueError("centre_draw: a negative number of draws")
+        if source.numel() == 0 and num_draws:
+            raise ValueError("centre_draw: draws from an empty volume")
+        pairs = [] if label_table is None else [(float(value), float(weight)) for value, weight in label_table]
+        if len(pairs) > _abi.CENTRE_MAX_LABELS:
+            raise ValueError(f"centre_draw: a label table of {len(pairs)} entries (at most {_abi.CENTRE_MAX_LABELS})")
+        values = (C.c_double * max(len(pairs), 1))(*[value for value, _ in pairs])
+        weights = (C.c_float * max(len(pairs), 1))(*[weight for _, weight in pairs])
+        source = source.contiguous()
+        if uniforms is not None:
+            if uniforms.dtype != torch.float64 or tuple(uniforms.shape) != (num_draws,):
+                raise ValueError(f"centre_draw: uniforms must be float64 of shape ({num_draws},), got {uniforms.dtype} {tuple(uniforms.shape)}")
+            uniforms = uniforms.contiguous()
+        self._check("centre_draw", source, uniforms)
+        device = source.device
+        segments = (source.numel() + _abi.CENTRE_SEGMENT - 1) // _abi.CENTRE_SEGMENT
+        prefix = torch.empty((segments,), dtype=torch.float64, device=device)
+        corner_words = (3 * num_draws + 3) // 4 * 4  # (the record starts on a 16-byte boundary)
+        packed = torch.empty((corner_words + _abi.CENTRE_RECORD_BYTES // 4,), dtype=torch.int32, device=device)
+        centres = torch.empty((num_draws,), dtype=torch.int64, device=device)
+        used = torch.empty((num_draws,), dtype=torch.float64, device=device) if return_uniforms else None
+        corners, record = packed[: 3 * num_draws].view(num_draws, 3), packed[corner_words:]
+        law = (_ptr(source), dtype_code(source.dtype), int(label_table is not None), values, weights, len(pairs), _i32x3(source.shape), _i32x3(patch))
+        self._call("centre_law_sums", source, *law, _ptr(prefix), _ptr(record), self._stream(source))
+        if num_draws:
+            self._call("centre_draw", source, *law, _ptr(prefix), _ptr(record), num_draws, int(seed) & (2**64 - 1), _ptr(uniforms), _ptr(used),
+                       _ptr(centres), _ptr(corners), self._stream(source))
+        return CentreDraw(centres, corners, record, packed, used, prefix)
+
+    def patch_gather(self, data: Tensor, corners: Tensor, patch_size: Sequence[int]) -> Tensor:
+        """``torch.stack([data[:, i:i + pi, j:j + pj, k:k + pk] for (i, j, k) in corners])`` in ONE launch (``tio_patch_gather``).
+
+        ``data``: ``(C, I, J, K)`` of any dtype (moved by element width); ``corners``: int32 ``(N, 3)``, on the device as a
+        draw leaves them or on the host (one small staged upload); a corner outside ``[0, shape - patch]`` is clamped by the
+        kernel.  Returns ``(N, C, pi, pj, pk)``.
+        """
+        if data.ndim != 4:
+            raise ValueError(f"patch_gather: expected a (C, I, J, K) tensor, got {tuple(data.shape)}")
+        patch = [int(p) for p in patch_size]
+        shape = [int(s) for s in data.shape[1:]]
+        if len(patch) != 3 or any(p < 1 for p in patch):
+            raise ValueError(f"patch_gather: patch_size must be three positive integers, got {tuple(patch_size)}")
+        if any(p > s for p, s in zip(patch, shape, strict=True)):
+            raise ValueError(f"Patch size {tuple(patch)} cannot be larger than spatial shape {tuple(shape)}")
+        if corners.ndim != 2 or corners.shape[1] != 3 or corners.dtype != torch.int32:
+            raise ValueError(f"patch_gather: corners must be int32 of shape (N, 3), got {corners.dtype} {tuple(corners.shape)}")
+        data = data.contiguous()
+        corners = h2d(corners, data.device).contiguous()
+        self._check("patch_gather", data, corners)
+        out = torch.empty((corners.shape[0], data.shape[0], *patch), dtype=data.dtype, device=data.device)
+        self._call("patch_gather", data, _ptr(data), _ptr(out), data.element_size(), data.shape[0], _i32x3(shape), _i32x3(patch), _ptr(corners),
+                   corners.shape[0], self._stream(data))
+        return out
+
+
+class CentreDraw(NamedTuple):
+    """What :meth:`Engine.centre_draw` leaves on the device."""
+
+    centres: Tensor  # int64 (N,): flat index of each centre, -1 where the law holds no positive weight
+    corners: Tensor  # int32 (N, 3): min(max(centre - patch // 2, 0), shape - patch); a view of `packed`
+    record: Tensor  # int32 (4,): the float64 total (two words) and the invalid flag; a view of `packed`
+    packed: Tensor  # corners, padding to 16 bytes, record: ONE copy brings both to the host
+    uniforms: Tensor | None  # float64 (N,): the uniforms used, when asked for
+    prefix: Tensor  # float64 (segments,): inclusive prefix sums of the segment totals
+
+    def on_host(self) -> tuple[Tensor, float, bool]:
+        """``(corners, total, invalid)`` on the host: the one device-to-host copy (and synchronisation) of a draw."""
+        host = self.packed.cpu()
+        record = host[host.numel() - _abi.CENTRE_RECORD_BYTES // 4 :]
+        return host[: self.corners.numel()].view(-1, 3), float(record[:2].view(torch.float64).item()), bool(record[2].item())
 
 
 _ENGINE: Engine | None = None
