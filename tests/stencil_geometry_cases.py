@@ -1,7 +1,7 @@
 """Launch geometries of the separable stencil: the cases of ``tests/test_stencil_passes.py`` (CPU) and
 ``tests/test_gpu_stencil_geometry.py`` (GPU), their inputs, their float64 reference and its error bound.
 
-The dispatcher (``plan_conv`` in ``torchio_amd/csrc/intensity.hip``) picks the kernel family and the number of marching segments
+The dispatcher (``plan_conv`` in ``torchio_amd/csrc/stencil.hip``) picks the kernel family and the number of marching segments
 per line from COUNTS: for the register-window marching kernel
 
     strips = ceil(K / 256) * other * B * C,  want = clamp(ceil(8192 / strips), 1, max(1, n / 32)),
@@ -112,6 +112,9 @@ def _sweep() -> dict:
         t[f"march_8x32_r{r}_I"] = _thin(s, r, rs, rk, False, ("march", 8, 32), short_rows=16, bias_i_pass=ring_i,
                                         per_element_taps=r == 7)
         t[f"march_8x32_r{r}_J"] = _thin(s, r, rs, rk, True, ("march", 8, 32), short_rows=16, per_element_taps=r == 6)
+    # radius class 5, the one class the shapes above leave out: its plain and its bias-on-load instantiation, exact and fused
+    # multiply-add, at the small shape of test_gpu_stencil_fused_codegen (37 is prime and above two windows: one march of 37 rows)
+    t["march_1x37_r5_I"] = _thin((2, 1, 37, 37, 8), 5, 2, 3, False, ("march", 1, 37), short_rows=37, per_element_taps=True)
     s = (64, 2, 250, 16, 8)  # 4 x 63, last segment 61
     t["march_4x63_ragged_r6_I"] = _thin(s, 6, 2, 1, False, ("march", 4, 63), short_rows=16)
     t["march_4x63_ragged_r4_J"] = _thin(s, 4, 1, 4, True, ("march", 4, 63), short_rows=16)

@@ -73,7 +73,7 @@ def _plan_ahead(hip, geometry, *, precision, level):
 
 
 def _listed(plan) -> int:
-    """Word 0 of the plan's header: the number of multi-pass bricks listed for the walkers (resample_fast.hpp: the plan)."""
+    """Word 0 of the plan's header: the number of multi-pass bricks listed for the walkers (resample_plan.hpp: the plan)."""
     torch.cuda.synchronize()
     return int(plan[0])
 

@@ -1,4 +1,4 @@
-"""The planned-brick roads of `tio_resample3d` (resample_fast.hpp): large launches only by default, forced here.
+"""The planned-brick roads of `tio_resample3d` (resample_plan.hpp): large launches only by default, forced here.
 
 * FAST: `plan_bricks_kernel` + `resample_planned_kernel` against the exact kernel (1e-4 relative, the north-star
   tolerance) and against the brick kernel's FAST instantiation it replaces for large launches.

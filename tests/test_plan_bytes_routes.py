@@ -25,7 +25,7 @@ from torchio_amd import _abi, _lib
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "plan_bytes_routes.json")
 
-PLAN_HEADER_INTS, DESC_INTS, PASS_INTS, PASSES_PER_BRICK = 16, 16, 8, 4  # resample_fast.hpp / resample_tile.hpp
+PLAN_HEADER_INTS, DESC_INTS, PASS_INTS, PASSES_PER_BRICK = 16, 16, 8, 4  # resample_plan.hpp / resample_tile.hpp
 
 #: every switch that takes part in the route choice: cleared for each case, then the case's own are set
 SWITCHES = ("TIO_FAST_KERNEL", "TIO_EXACT_LEAN", "TIO_EXACT_PLAN", "TIO_PLANNED_LEAN", "TIO_LEAN_MULTI", "TIO_RESAMPLE_PATH",

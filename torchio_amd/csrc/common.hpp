@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/tio_hip.h"
 
 namespace tio {
@@ -211,6 +213,16 @@ template <typename F>
   }
 }
 
+// run-time booleans -> template arguments: f is called with one std::bool_constant per flag, in the order given
+// (every combination of the flags is instantiated: pass only flags whose whole cross product exists)
+template <typename F>
+auto with_bools(F f) { return f(); }
+template <typename F, typename... Rest>
+auto with_bools(F f, bool first, Rest... rest) {
+  return first ? with_bools([&](auto... c) { return f(std::true_type{}, c...); }, rest...)
+               : with_bools([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
+}
+
 // The unsigned integer of ES bytes: what a kernel that only moves elements loads and stores.
 template <int ES> struct RawBits;
 template <> struct RawBits<1> { typedef uint8_t type; };
@@ -265,7 +277,7 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nblocks) {
 }
 
 
-// Per-channel minimum through ordered-integer keys (intensity.hip: tio_channel_min; resample_fast.hpp: the minimum of a
+// Per-channel minimum through ordered-integer keys (intensity.hip: tio_channel_min; resample_line.hpp, resample_plan.hpp: the minimum of a
 // resampler's own output, folded into its stores).  NaN maps to key 0 so it wins, matching torch.min's NaN propagation.
 __device__ __forceinline__ uint32_t float_to_key(float f) {
   if (f != f) return 0u;

@@ -1,5 +1,5 @@
 // philox_normal.hpp — the fast-mode normal stream (Philox4x32-10 + Box-Muller), shared by intensity.hip (tio_add_noise,
-// tio_philox_normal, the stencil's fused noise) and labels_to_image.hip: one definition, one stream.
+// tio_philox_normal), the stencil (stencil_march.hpp, stencil.hip: the fused noise) and labels_to_image.hip: one definition, one stream.
 #pragma once
 
 #include "common.hpp"

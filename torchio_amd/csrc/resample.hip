@@ -607,11 +607,13 @@ __global__ __launch_bounds__(kRowsPerBlock* kLanes) void resample_kernel(const R
 
 #include "resample_exact_chain.hpp"
 #include "resample_tile.hpp"
+#include "resample_line.hpp"
+#include "resample_plan.hpp"
 #include "resample_fast.hpp"
 #include "resample_lean_exact.hpp"
 #include "resample_nearest.hpp"
 
-// Device scratch for the brick plan of a planned launch (resample_fast.hpp): one buffer per (device, stream), grown on
+// Device scratch for the brick plan of a planned launch (resample_plan.hpp): one buffer per (device, stream), grown on
 // demand and kept.  A planned launch is a PAIR of kernels on the caller's stream — plan_bricks_kernel writes the buffer,
 // the sampling kernel reads it — so the buffer is LEASED: the lease holds the slot's mutex from the lookup until both
 // kernels are enqueued.  Two host threads that share a stream (the reference's Queue workers on the default stream,
@@ -670,16 +672,6 @@ static PlanLease plan_workspace(hipStream_t s, size_t bytes) {
 // group's road; tio_resample3d_plan_bytes / tio_resample3d_plan ask it the same question for one aligned float32 image.
 namespace {
 using namespace tio;
-
-// run-time booleans -> template arguments: f is called with one std::bool_constant per flag, in the order given
-// (every combination of the flags is instantiated: pass only flags whose whole cross product exists)
-template <typename F>
-auto with_bools(F f) { return f(); }
-template <typename F, typename... Rest>
-auto with_bools(F f, bool first, Rest... rest) {
-  return first ? with_bools([&](auto... c) { return f(std::true_type{}, c...); }, rest...)
-               : with_bools([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
-}
 
 using RowsKernel = void (*)(ResampleArgs);               // resample_kernel
 using BrickKernel = void (*)(ResampleArgs, const int*);  // resample_tile_kernel, resample_planned_kernel
@@ -952,7 +944,7 @@ FloatRoad choose_float_road(const tio_resample_geom& geom, const ResampleArgs& a
   const bool lean_exact = !fast && (tight || ((geom.precision == TIO_PRECISION_EXACT || geom.precision == TIO_PRECISION_TIGHT) && env.exact_lean != 0)) &&
                           g.dtmode == 0 && !a.any_nearest && r.ablate == 0 && a.short_div != 0 && (a.cp == nullptr || a.unit_spacing != 0);
   if (fast || lean_exact) {
-    // Planned bricks (resample_fast.hpp): a planning kernel, then one block per brick that starts from its 64-byte descriptor. Needs 16-byte rows for the LDS-DMA and
+    // Planned bricks (resample_plan.hpp): a planning kernel, then one block per brick that starts from its 64-byte descriptor. Needs 16-byte rows for the LDS-DMA and
     // control cells at least a brick wide (the box comes from <= 27 vertices); small launches keep the single-kernel road (the planning kernel and the gap before the
     // second launch cost ~10-15 us, more than the planned bricks save below ~12 k bricks).  TIO_FAST_KERNEL=planned forces them, =brick keeps FAST launches off them (A/B).
     const bool force_planned = lean_exact ? (env.fast_kernel == 2 || env.exact_lean == 2) : env.fast_kernel == 2;

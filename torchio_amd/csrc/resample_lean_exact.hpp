@@ -25,13 +25,13 @@
 //                        the volume, so `mask > 0.5` is the reference's decision by construction — no recheck tail).
 //                        Differs from the reference by the rounding of seven fused multiply-adds: ~1e-7 of the taps.
 //
-// Included by resample.hip after resample_fast.hpp (planner, LeanArgs, StreamBox, StageLanes) and resample_tile.hpp
+// Included by resample.hip after resample_plan.hpp (planner, LeanArgs, StreamBox, StageLanes) and resample_tile.hpp
 // (TapSet, TileAddr, tile_issue_interior, tile_finish*, tile_mask, cp_plane, normalise_roundtrip_folded).
 #pragma once
 
 namespace tio {
 
-// ---- the packed LDS-DMA of one box as a STEPPER: the same instruction sequence as stream_stage_packed (resample_fast.hpp),
+// ---- the packed LDS-DMA of one box as a STEPPER: the same instruction sequence as stream_stage_packed (resample_plan.hpp),
 // one instruction per call, so that the caller can put arithmetic between two of them ------------------------------------
 // every vector-memory AND LDS operation of this wave done (the zero chunks of BoxDmaStepper::issue<false> are LDS stores the
 // compiler does not know about)
@@ -331,7 +331,7 @@ template <bool GUARD, bool TRACK>
 __device__ __forceinline__ void lean_exact_group_store(const float (&vals)[4], char*& out_generic, unsigned urow, int64_t slab_b, int t0, int i_count,
                                                        bool col_active, uint32_t& kmin) {
   typedef __attribute__((address_space(1))) char* global_char_ptr;   // (typed global: a flat store would count on lgkmcnt too —
-  typedef __attribute__((address_space(1))) float* global_float_ptr;  //  resample_fast.hpp: fast_sample_run)
+  typedef __attribute__((address_space(1))) float* global_float_ptr;  //  resample_line.hpp: fast_sample_run)
   global_char_ptr out_t = (global_char_ptr)out_generic;
   // (the row offset re-enters the block as a 32-bit register: instruction selection works block by block, and only a zero
   // extension it can SEE lets the store take the `scalar base + 32-bit vector offset` form — otherwise one 64-bit vector add per store)

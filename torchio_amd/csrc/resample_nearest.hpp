@@ -1,13 +1,13 @@
 // Nearest-neighbour images without a fill rule (label maps, masks): their own kernel, bit-identical to the exact
 // coordinate chain at a fraction of its cost.  Included by resample.hip after the exact-chain helpers (exact_div,
-// normalise_roundtrip, cp_trilerp3) and resample_fast.hpp.
+// normalise_roundtrip, cp_trilerp3) and resample_line.hpp, resample_plan.hpp.
 //
 // Reference: `_sample_batch_grid_sample(..., mode="nearest")` -> F.grid_sample(padding_mode="zeros", align_corners=True)
 // (transforms/spatial/spatial.py:1695-1731): the value of the input voxel at nearbyint(coordinate) per axis, zero
 // outside.  The result depends on the coordinate only through three roundings, so the float32 op sequence of the
 // reference's chain (affine_grid-style matmul, field upsampling, normalise / un-normalise: ~115 vector instructions per
 // voxel with control points) matters only where a coordinate lies within rounding error of a half-integer.  The kernel
-//   1. evaluates the FAST coordinate line of the column (resample_fast.hpp: one fma per axis and plane),
+//   1. evaluates the FAST coordinate line of the column (resample_line.hpp: one fma per axis and plane),
 //   2. takes the voxel as decided when on every axis |x - rint(x)| <= 1/2 - margin, margin = kNearestEps (row + S + |x|)
 //      with row = sum |m_rc| S_out,c + |m_r3| (every partial sum of the reference's matmul is below it) — the rounding, and
 //      the in-bounds test (it flips at -1/2 and S - 1/2: half-integers too), are then the same for any coordinate within

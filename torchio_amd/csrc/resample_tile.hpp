@@ -259,7 +259,7 @@ __device__ __forceinline__ void gather_voxel(const ImgArgs& g, const ResampleArg
 }
 
 // ---- the staged box of one pass (block uniform, kept in SGPRs) -------------------------
-// The brick plan written by plan_bricks_kernel (resample_fast.hpp): 16 dwords per brick after 16 floats per batch element
+// The brick plan written by plan_bricks_kernel (resample_plan.hpp): 16 dwords per brick after 16 floats per batch element
 enum : int { kDescInts = 16, kDescStaged = 0, kDescOutside = 1, kDescSlow = 2, kDescGated = 3 };
 
 struct TileBox {

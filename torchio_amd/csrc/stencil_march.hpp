@@ -1,7 +1,7 @@
 // stencil_march.hpp - the register-window marching kernel of the separable stencil (axes I and J, radii <= 8) and its
 // argument block.  A header because the kernel's two families are compiled in two translation units with different code
-// generation (see the Makefile): intensity.hip holds the plain I / J and the bias-on-load instantiations and every other
-// stencil kernel, stencil_fused.hip the fused J + K ones.  The launcher in intensity.hip decides; this file decides nothing.
+// generation (see the Makefile): stencil.hip holds the plain I / J and the bias-on-load instantiations and every other
+// stencil kernel, stencil_fused.hip the fused J + K ones.  The launcher in stencil.hip decides; this file decides nothing.
 #pragma once
 
 #include "common.hpp"
@@ -322,6 +322,23 @@ __global__ __launch_bounds__(kBlock, (FUSE_K && !PRE_BIAS && R <= 6) ? 4 : 1) vo
   }
 #undef TIO_ROW_LOAD
 #undef TIO_ROW_POS
+}
+
+// run-time radius class -> template argument: f is called with std::integral_constant<int, R> for radius_class R = 1 .. 7,
+// and with R = kMarchMaxRadius for every other value (both launchers instantiate all eight: the boolean template arguments
+// go through with_bools, common.hpp)
+template <typename F>
+void with_march_radius(int radius_class, F f) {
+  switch (radius_class) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 5: f(std::integral_constant<int, 5>{}); break;
+    case 6: f(std::integral_constant<int, 6>{}); break;
+    case 7: f(std::integral_constant<int, 7>{}); break;
+    default: f(std::integral_constant<int, kMarchMaxRadius>{}); break;
+  }
 }
 
 // The fused J + K instantiations <R, true, false, post_noise, fma> (stencil_fused.hip): radius_class 1 .. 8, post_noise 0 / 1 / 2.

@@ -435,7 +435,7 @@ class Engine:
         # (tio_resample_image.out_min_dev), which is what the NEXT spatial transform's default_pad_value="minimum" will ask
         # of exactly this tensor (`folded_channel_min`).  Requested when somebody has announced that consumer
         # (`expect_minimum_fill`: a Compose that draws ahead knows its next child) or with TIO_FOLDED_MIN=1; only the bricks of
-        # element 0 track what they store, in an instantiation of its own (resample_fast.hpp), and a ~2 us kernel decodes the
+        # element 0 track what they store, in an instantiation of its own, and a ~2 us kernel (resample_plan.hpp: min_finish_kernel) decodes the
         # result: it replaces the ~21 us reduction and its re-read of the volume.  Requested only where the C side folds it
         # (the rule of resample.hip's planned path, mirrored loosely: a miss costs one tio_channel_min launch, never a wrong
         # value).

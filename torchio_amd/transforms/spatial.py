@@ -699,7 +699,7 @@ def _expects_large_boxes(mapping: np.ndarray | None, displacements, field_shape,
 
     The box of a brick under the output -> input voxel mapping ``M`` spans ``15 sum_c |M_rc|`` voxels along input axis ``r``
     (plus the displacement field's variation over the brick, plus the taps), rows padded to 16-byte chunks — the planner's
-    own arithmetic (csrc/resample_fast.hpp: plan_bricks_kernel) on the host copy of the mappings.  A HINT: it chooses between
+    own arithmetic (csrc/resample_plan.hpp: plan_bricks_kernel) on the host copy of the mappings.  A HINT: it chooses between
     roads that compute the same values (``TIO_GEOM_LARGE_BOXES`` / ``TIO_GEOM_MOSTLY_LARGE_BOXES``), so an estimate is enough."""
     if mapping is None:
         return 0
