@@ -29,56 +29,10 @@
 #include <vector>
 #include <algorithm>
 
-#include "common.hpp"
+#include "resample_args.hpp"
+#include "resample_coords.hpp"
 
 namespace tio {
-
-struct ImgArgs {
-  const void* in;
-  void* out;
-  const float* fill;  // nullptr → no mask step
-  int channels;
-  int dtype;
-  int interp;
-  // TIO_LABEL_PV only: sorted label table (may be null), its length, the pad label
-  const double* labels;
-  int n_labels;
-  double pad_label;
-  // the folded minimum (planned FAST launches): per-channel result, and this image's first key in the workspace
-  float* out_min;
-  uint32_t* min_keys;
-};
-
-struct ResampleArgs {
-  int B;
-  int I, J, K;
-  int Io, Jo, Ko;
-  int affine_first;
-  const float* mapping;
-  int mapping_batched;
-  const float* cp;
-  int cp_batched;
-  int ni, nj, nk;
-  const uint8_t* cp_skip;
-  const uint8_t* passthrough;
-  float sp[3], rsp[3];              // mm → voxel spacing and its float32 reciprocal
-  int unit_spacing;                 // all three spacings == 1.0f: d / 1 is the identity
-  float scale_i, scale_j, scale_k;  // ATen lerp scales of the control grid
-  float den[3], rden[3];            // max(S-1,1) per input axis and reciprocal
-  float size_m1[3];                 // S-1 per input axis
-  float dh[3], rdh[3], half_h[3];   // den/2, its reciprocal, (S-1)/2: the folded normalise round trip
-  int short_div;                    // every den <= 8192: one division refinement is exact
-  int any_linear, any_nearest;      // which coordinate products are needed at all
-  int n_images;
-  ImgArgs img[TIO_MAX_IMAGES];
-  int tiles_k, tiles_j, tiles_i;
-  unsigned magic_k, magic_j, magic_i;  // multiply-high reciprocals of the tile counts (tile kernel)
-  int cp_lds;    // floats of LDS reserved for the control points (0 = read them from global)
-  int tile_cap;  // floats of LDS available for one staged input brick (tile kernel)
-  int any_fill;      // an image of the launch has a fill rule
-  int plan_multi;    // plan_bricks_kernel: bricks whose box exceeds the tile get pass boxes over halves / quarters of their planes (the exact-coordinate lean kernel reads them)
-  int fill_recheck;  // FAST kernels: voxels whose in-bounds weight is within a margin of 1/2 take the exact chain's decision (A/B: TIO_FAST_FILL_RECHECK=0)
-};
 
 constexpr int kTileI = 8;          // output slabs walked by one block
 constexpr int kRowsPerBlock = 4;   // one wave per output row (jo)
@@ -88,52 +42,6 @@ constexpr int kLdsFloatsPerCU = 40960;   // 160 KiB
 constexpr int kPlannedMinBricks = 12288;  // below: one kernel with in-kernel boxes (the plan costs a launch)
 constexpr int kTileMinCap = 6144;       // the per-voxel fallback parks 8 planes x 3 coordinates x 256 threads there
 constexpr int kTileBlocksPerCU = 3;       // resident blocks the default LDS budget is sized for
-
-// IEEE-754 correctly rounded n / d from r = RN(1/d): q0 = RN(n r), two Markstein
-// refinements (each: exact remainder by FMA, correction by FMA).  Checked
-// bit-for-bit against the hardware division on 1.9e9 operands (integer
-// divisors 1..2100, spacings in [0.05, 20], exact-multiple neighbourhoods).
-__device__ __forceinline__ float exact_div(float n, float d, float r) {
-  float q = __fmul_rn(n, r);
-  float e = __builtin_fmaf(-d, q, n);
-  q = __builtin_fmaf(e, r, q);
-  e = __builtin_fmaf(-d, q, n);
-  return __builtin_fmaf(e, r, q);
-}
-
-// g = 2 v / max(S-1,1) - 1 (spatial.py:1638-1646) followed by ATen's
-// grid_sampler_unnormalize(align_corners=True): ((g + 1) / 2) * (S - 1).
-__device__ __forceinline__ float normalise_roundtrip(float v, float den, float rden, float size_m1) {
-  const float g = __fsub_rn(exact_div(__fmul_rn(2.0f, v), den, rden), 1.0f);
-  return __fmul_rn(__fmul_rn(__fadd_rn(g, 1.0f), 0.5f), size_m1);
-}
-
-// trilinear lookup of the three displacement components from the (ni,nj,nk,3)
-// field; nesting and rounding exactly as ATen's upsample_trilinear3d (K innermost)
-struct Disp {
-  float i, j, k;
-};
-
-__device__ __forceinline__ Disp cp_trilerp3(const float* __restrict__ cp, int s_i, int s_j, const Lerp1D& li,
-                                            const Lerp1D& lj, const Lerp1D& lk) {
-  const float* p00 = cp + li.i0 * s_i + lj.i0 * s_j;
-  const float* p01 = cp + li.i0 * s_i + lj.i1 * s_j;
-  const float* p10 = cp + li.i1 * s_i + lj.i0 * s_j;
-  const float* p11 = cp + li.i1 * s_i + lj.i1 * s_j;
-  const int k0 = lk.i0 * 3, k1 = lk.i1 * 3;
-  float r[3];
-#pragma unroll
-  for (int c = 0; c < 3; c++) {
-    const float a00 = lerp2(p00[k0 + c], lk.l0, p00[k1 + c], lk.l1);
-    const float a01 = lerp2(p01[k0 + c], lk.l0, p01[k1 + c], lk.l1);
-    const float a10 = lerp2(p10[k0 + c], lk.l0, p10[k1 + c], lk.l1);
-    const float a11 = lerp2(p11[k0 + c], lk.l0, p11[k1 + c], lk.l1);
-    const float b0 = lerp2(a00, lj.l0, a01, lj.l1);
-    const float b1 = lerp2(a10, lj.l0, a11, lj.l1);
-    r[c] = lerp2(b0, li.l0, b1, li.l1);
-  }
-  return Disp{r[0], r[1], r[2]};
-}
 
 // ---- sampling --------------------------------------------------------------------
 // Interior path: every tap of every lane of the wave is in bounds, so there is no
@@ -468,10 +376,6 @@ __global__ __launch_bounds__(kRowsPerBlock* kLanes) void resample_kernel(const R
   for (int io = i_begin; io < i_end; io++) {
     const float ci = static_cast<float>(io);
     float vi, vj, vk;
-    // [c,1] @ M^T per row: a*m0, then fma(b,m1,.), fma(c,m2,.), fma(1,m3,.) — the
-    // rounding sequence of MKL sgemm (K = 4), pinned against the reference.
-#define TIO_AFFINE_ROW(M0, M1, M2, M3, A, B, C) \
-  __builtin_fmaf(1.0f, M3, __builtin_fmaf(C, M2, __builtin_fmaf(B, M1, __fmul_rn(A, M0))))
     bool done = false;
     if constexpr (ELASTIC_POSSIBLE) {
       if (elastic) {
@@ -501,7 +405,6 @@ __global__ __launch_bounds__(kRowsPerBlock* kLanes) void resample_kernel(const R
       vj = TIO_AFFINE_ROW(m10, m11, m12, m13, ci, cj, ck);
       vk = TIO_AFFINE_ROW(m20, m21, m22, m23, ci, cj, ck);
     }
-#undef TIO_AFFINE_ROW
     if constexpr (MODE == 2) {  // grid_pull takes the voxel coordinates as they are (spatial.py:1749-1760)
       const int64_t o_idx = io * slab + row;
       for (int im = 0; im < a.n_images; im++) {

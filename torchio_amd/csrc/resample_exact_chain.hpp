@@ -13,9 +13,8 @@
 //     and overwrites what the loop stored (same thread, same address: program order).  The tail is behind the loops
 //     because inlined into them the exact chain's registers add to the hot loop's (a first version: 95 -> 157 VGPRs
 //     and 27 spilled SGPRs in the lean kernel); behind them the kernel needs the larger of the two, not the sum.
-//
-// Included by resample.hip after the helpers of the exact kernels (exact_div, normalise_roundtrip, cp_trilerp3).
 #pragma once
+#include "resample_coords.hpp"
 
 namespace tio {
 
@@ -34,8 +33,6 @@ __device__ __forceinline__ void exact_voxel_coords(const Args& a, const float (&
                                                    float& z) {
   const float ci = static_cast<float>(io);
   float vi = 0.0f, vj = 0.0f, vk = 0.0f;
-#define TIO_AFFINE_ROW(M0, M1, M2, M3, A, B, C) \
-  __builtin_fmaf(1.0f, M3, __builtin_fmaf(C, M2, __builtin_fmaf(B, M1, __fmul_rn(A, M0))))
   bool done = false;
   if constexpr (ELASTIC_POSSIBLE) {
     if (elastic) {
@@ -65,7 +62,6 @@ __device__ __forceinline__ void exact_voxel_coords(const Args& a, const float (&
     vj = TIO_AFFINE_ROW(m[4], m[5], m[6], m[7], ci, cj, ck);
     vk = TIO_AFFINE_ROW(m[8], m[9], m[10], m[11], ci, cj, ck);
   }
-#undef TIO_AFFINE_ROW
   x = normalise_roundtrip(vi, a.den[0], a.rden[0], a.size_m1[0]);
   y = normalise_roundtrip(vj, a.den[1], a.rden[1], a.size_m1[1]);
   z = normalise_roundtrip(vk, a.den[2], a.rden[2], a.size_m1[2]);

@@ -25,8 +25,13 @@
 //
 // This file holds only the kernels that TIO_PRECISION_FAST alone reaches.  The line coordinates they share with the exact
 // lean and nearest kernels are in resample_line.hpp; the planner, the plan layout, the LDS-DMA helpers and LeanArgs, which
-// every planned launch uses, are in resample_plan.hpp.  Included by resample.hip after both.
+// every planned launch uses, are in resample_plan.hpp.
 #pragma once
+#include "resample_args.hpp"
+#include "resample_exact_chain.hpp"
+#include "resample_tile.hpp"
+#include "resample_line.hpp"
+#include "resample_plan.hpp"
 
 namespace tio {
 

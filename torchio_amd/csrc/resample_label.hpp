@@ -16,7 +16,7 @@
 // two more levels); only positions of non-zero channels matter, hence the label table.
 #pragma once
 
-#include "common.hpp"
+#include "resample_coords.hpp"
 
 namespace tio {
 
@@ -100,15 +100,6 @@ struct CascadeSum {
   }
 };
 
-__device__ __forceinline__ uint64_t label_bits(const void* p, int es, int64_t i) {
-  switch (es) {
-    case 1: return static_cast<const uint8_t*>(p)[i];
-    case 2: return static_cast<const uint16_t*>(p)[i];
-    case 4: return static_cast<const uint32_t*>(p)[i];
-    default: return static_cast<const uint64_t*>(p)[i];
-  }
-}
-
 // Everything a voxel needs besides its coordinates (plain scalars: nothing lives in memory,
 // so the call to the general path below does not force the caller's arrays into scratch).
 struct LabelSite {
@@ -130,14 +121,7 @@ __device__ __forceinline__ unsigned label_taps(const LabelSite& s, float x, floa
   const float wx0 = x1 - x, wx1 = x - x0;
   const float wy0 = y1 - y, wy1 = y - y0;
   const float wz0 = z1 - z, wz1 = z - z0;
-  w[0] = __fmul_rn(__fmul_rn(wx0, wy0), wz0);
-  w[1] = __fmul_rn(__fmul_rn(wx1, wy0), wz0);
-  w[2] = __fmul_rn(__fmul_rn(wx0, wy1), wz0);
-  w[3] = __fmul_rn(__fmul_rn(wx1, wy1), wz0);
-  w[4] = __fmul_rn(__fmul_rn(wx0, wy0), wz1);
-  w[5] = __fmul_rn(__fmul_rn(wx1, wy0), wz1);
-  w[6] = __fmul_rn(__fmul_rn(wx0, wy1), wz1);
-  w[7] = __fmul_rn(__fmul_rn(wx1, wy1), wz1);
+  corner_weights(wx0, wx1, wy0, wy1, wz0, wz1, w);
   const bool bx0 = (x0 >= 0.0f) & (x0 <= s.hx), bx1 = (x1 >= 0.0f) & (x1 <= s.hx);
   const bool by0 = (y0 >= 0.0f) & (y0 <= s.hy), by1 = (y1 >= 0.0f) & (y1 <= s.hy);
   const bool bz0 = (z0 >= 0.0f) & (z0 <= s.hz), bz1 = (z1 >= 0.0f) & (z1 <= s.hz);

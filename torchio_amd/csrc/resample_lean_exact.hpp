@@ -25,9 +25,14 @@
 //                        the volume, so `mask > 0.5` is the reference's decision by construction — no recheck tail).
 //                        Differs from the reference by the rounding of seven fused multiply-adds: ~1e-7 of the taps.
 //
-// Included by resample.hip after resample_plan.hpp (planner, LeanArgs, StreamBox, StageLanes) and resample_tile.hpp
-// (TapSet, TileAddr, tile_issue_interior, tile_finish*, tile_mask, cp_plane, normalise_roundtrip_folded).
+// Built on resample_coords.hpp (exact_div, cp_plane, normalise_roundtrip_folded), resample_plan.hpp (planner, LeanArgs, StreamBox,
+// StageLanes) and resample_tile.hpp (TapSet, TileAddr, tile_issue_interior, tile_finish*, tile_mask).
 #pragma once
+#include "resample_coords.hpp"
+#include "resample_exact_chain.hpp"
+#include "resample_tile.hpp"
+#include "resample_line.hpp"
+#include "resample_plan.hpp"
 
 namespace tio {
 
@@ -107,15 +112,13 @@ struct BoxDmaStepper {
 //   MODE 1: displacement on an identity mapping (ElasticDeformation alone): c + d either way round
 //   MODE 2: affine first (spatial.py:1570-1573)      MODE 3: elastic first (spatial.py:1574-1577)
 // UNIT: all three spacings are 1.0f (d / 1 is the identity); SHORT: one Markstein refinement is the correctly rounded
-// quotient for this launch's divisors (resample_tile.hpp: normalise_roundtrip_folded, tests/native/divtest.c)
+// quotient for this launch's divisors (resample_coords.hpp: normalise_roundtrip_folded, tests/native/divtest.c)
 template <int MODE, bool UNIT, bool SHORT>
 __device__ __forceinline__ void lean_exact_coord(const float (&m)[12], const LeanArgs& a, float ci, float cj, float ck, float di, float dj,
                                                  float dk, float& x, float& y, float& z) {
-#define TIO_LE_ROW(R, A, B, C) \
-  __builtin_fmaf(1.0f, m[4 * R + 3], __builtin_fmaf(C, m[4 * R + 2], __builtin_fmaf(B, m[4 * R + 1], __fmul_rn(A, m[4 * R]))))
   float vi, vj, vk;
   if constexpr (MODE == 0) {
-    vi = TIO_LE_ROW(0, ci, cj, ck); vj = TIO_LE_ROW(1, ci, cj, ck); vk = TIO_LE_ROW(2, ci, cj, ck);
+    vi = TIO_AFFINE_ROW(m[0], m[1], m[2], m[3], ci, cj, ck); vj = TIO_AFFINE_ROW(m[4], m[5], m[6], m[7], ci, cj, ck); vk = TIO_AFFINE_ROW(m[8], m[9], m[10], m[11], ci, cj, ck);
   } else {
     float qi = di, qj = dj, qk = dk;
     if constexpr (!UNIT) {
@@ -126,15 +129,14 @@ __device__ __forceinline__ void lean_exact_coord(const float (&m)[12], const Lea
     if constexpr (MODE == 1) {
       vi = __fadd_rn(ci, qi); vj = __fadd_rn(cj, qj); vk = __fadd_rn(ck, qk);
     } else if constexpr (MODE == 2) {
-      vi = __fadd_rn(TIO_LE_ROW(0, ci, cj, ck), qi);
-      vj = __fadd_rn(TIO_LE_ROW(1, ci, cj, ck), qj);
-      vk = __fadd_rn(TIO_LE_ROW(2, ci, cj, ck), qk);
+      vi = __fadd_rn(TIO_AFFINE_ROW(m[0], m[1], m[2], m[3], ci, cj, ck), qi);
+      vj = __fadd_rn(TIO_AFFINE_ROW(m[4], m[5], m[6], m[7], ci, cj, ck), qj);
+      vk = __fadd_rn(TIO_AFFINE_ROW(m[8], m[9], m[10], m[11], ci, cj, ck), qk);
     } else {
       const float ei = __fadd_rn(ci, qi), ej = __fadd_rn(cj, qj), ek = __fadd_rn(ck, qk);
-      vi = TIO_LE_ROW(0, ei, ej, ek); vj = TIO_LE_ROW(1, ei, ej, ek); vk = TIO_LE_ROW(2, ei, ej, ek);
+      vi = TIO_AFFINE_ROW(m[0], m[1], m[2], m[3], ei, ej, ek); vj = TIO_AFFINE_ROW(m[4], m[5], m[6], m[7], ei, ej, ek); vk = TIO_AFFINE_ROW(m[8], m[9], m[10], m[11], ei, ej, ek);
     }
   }
-#undef TIO_LE_ROW
   x = normalise_roundtrip_folded<SHORT>(vi, a.dh[0], a.rdh[0], a.half_h[0]);
   y = normalise_roundtrip_folded<SHORT>(vj, a.dh[1], a.rdh[1], a.half_h[1]);
   z = normalise_roundtrip_folded<SHORT>(vk, a.dh[2], a.rdh[2], a.half_h[2]);

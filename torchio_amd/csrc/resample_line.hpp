@@ -3,8 +3,10 @@
 // brick, the displacement and coordinate of a point in it, the cell breakpoints, the eight-tap gather from a staged box with
 // its separable fill rule, and the per-column line through a run of planes.  Used by the FAST kernels (resample_fast.hpp),
 // by the planner (resample_plan.hpp: the vertices of a brick), by the lean exact kernel (resample_lean_exact.hpp) and by the
-// exact nearest kernel (resample_nearest.hpp).  Included by resample.hip after resample_tile.hpp.
+// exact nearest kernel (resample_nearest.hpp).
 #pragma once
+#include "resample_coords.hpp"
+#include "resample_tile.hpp"
 
 namespace tio {
 
@@ -31,7 +33,6 @@ struct FastFrameT {
   float sci, scj, sck;    // control-grid lerp scales
   float dsc[3];           // displacement scale: 1 / spacing (times the axis ratio when affine_first)
 };
-typedef FastFrameT<fast_lds_ptr> FastFrame;
 
 // displacement (already in voxels) at the volume position (i, j, k), any of them fractional
 template <typename CP>

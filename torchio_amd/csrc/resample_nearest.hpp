@@ -1,6 +1,5 @@
 // Nearest-neighbour images without a fill rule (label maps, masks): their own kernel, bit-identical to the exact
-// coordinate chain at a fraction of its cost.  Included by resample.hip after the exact-chain helpers (exact_div,
-// normalise_roundtrip, cp_trilerp3) and resample_line.hpp, resample_plan.hpp.
+// coordinate chain at a fraction of its cost.
 //
 // Reference: `_sample_batch_grid_sample(..., mode="nearest")` -> F.grid_sample(padding_mode="zeros", align_corners=True)
 // (transforms/spatial/spatial.py:1695-1731): the value of the input voxel at nearbyint(coordinate) per axis, zero
@@ -13,11 +12,17 @@
 //      the in-bounds test (it flips at -1/2 and S - 1/2: half-integers too), are then the same for any coordinate within
 //      `margin` of x; the FAST and the exact coordinate differ by less than a tenth of it (bound and measurement:
 //      DESIGN.md section 4.1b),
-//   3. re-evaluates the few undecided voxels of the column with the exact chain (exact_voxel_coords below: the
+//   3. re-evaluates the few undecided voxels of the column with the exact chain (exact_voxel_coords, resample_exact_chain.hpp: the
 //      operation sequence of resample_kernel, which tests/ pin against the oracle and the reference's golden vectors).
 // One load per voxel straight from global memory (no LDS: a nearest image has no taps to share), element size 1 / 2 / 4 / 8
 // bytes copied as bits, every image and channel of the launch that has that size.
 #pragma once
+#include "resample_coords.hpp"
+#include "resample_exact_chain.hpp"
+#include "resample_tile.hpp"
+#include "resample_line.hpp"
+#include "resample_plan.hpp"
+#include "resample_lean_exact.hpp"
 
 namespace tio {
 
@@ -51,9 +56,6 @@ struct NearestArgs {
   int n_images;
   NearestImg img[TIO_MAX_IMAGES];
 };
-
-// (exact_voxel_coords — the exact coordinate chain of ONE voxel — lives in resample_exact_chain.hpp: the FAST float kernels
-// use it as well, for the fill decision of voxels whose in-bounds weight is within rounding of 1/2)
 
 template <int ES> struct NearestCarrier { typedef uint32_t type; };  // what a loaded element travels in (a whole register)
 template <> struct NearestCarrier<8> { typedef uint64_t type; };
@@ -404,7 +406,6 @@ __device__ __forceinline__ typename RawBits<ES>::type nearest_buffer_load(__amdg
 template <bool ELASTIC_POSSIBLE, int ES>
 __global__ __launch_bounds__(256, 3) void resample_nearest_exact_kernel(const NearestArgs a) {
   typedef typename RawBits<ES>::type bits_t;
-  typedef typename NearestCarrier<ES>::type carrier_t;
   constexpr int TI = 16, TJ = 4, TK = 64;
   {
     const float* mp = a.mapping; const uint8_t* pp = a.passthrough; const float* cpp = a.cp;

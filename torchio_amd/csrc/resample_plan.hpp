@@ -2,17 +2,14 @@
 // kernel (plan_bricks_kernel, one group of lanes per brick: the staged box from the brick's vertices), the plan's layout,
 // the packed LDS-DMA that stages a planned box (StreamBox, StageLanes, stream_stage_packed), the decoder of the folded
 // minimum (min_finish_kernel) and the argument block of the lean kernels (LeanArgs).  The kernels that consume a plan are
-// in resample_tile.hpp, resample_fast.hpp, resample_lean_exact.hpp and resample_nearest.hpp.  Included by resample.hip
-// after resample_tile.hpp (box_address_fits, kTileFar) and resample_line.hpp (the frame and its vertices).
+// in resample_tile.hpp, resample_fast.hpp, resample_lean_exact.hpp and resample_nearest.hpp.  Built on
+// resample_tile.hpp (box_address_fits, kTileFar) and resample_line.hpp (the frame and its vertices).
 #pragma once
+#include "resample_args.hpp"
+#include "resample_tile.hpp"
+#include "resample_line.hpp"
 
 namespace tio {
-
-enum : int {
-  kSlabStaged = 0,   // box staged in LDS: sample from it
-  kSlabOutside = 1,  // the brick sees nothing of the volume: fill (or 0)
-  kSlabGather = 2    // non-finite geometry / box beyond the LDS budget: per-voxel global gather
-};
 
 struct StreamBox {
   int kind, bx0, by0, za, Lx, Ly, cpr, interior;

@@ -1,5 +1,5 @@
-// resample_tile.hpp — LDS-staged brick variant of the fused resampler (included by
-// resample.hip; shares its argument block and the float32 coordinate chain).
+// resample_tile.hpp — LDS-staged brick variant of the fused resampler (argument block:
+// resample_args.hpp; exact_div, the folded round trip, cp_plane: resample_coords.hpp).
 //
 // Why: the gather kernel issues 8 wave-wide dword gathers per output voxel; under a
 // rotation every one of them touches ~10 cache lines, so the texture-address path
@@ -27,6 +27,8 @@
 // float address arithmetic, endpoint bounding boxes for monotone (affine-only) columns,
 // DPP instead of shuffles, and no per-voxel selects.
 #pragma once
+#include "resample_args.hpp"
+#include "resample_coords.hpp"
 
 namespace tio {
 
@@ -96,44 +98,6 @@ __device__ __forceinline__ void block_max6(int (&r)[N], int* s_red, int slot, in
   }
 }
 
-// g = 2 v / max(S-1,1) - 1 then ATen's un-normalise ((g + 1) / 2) * (S - 1), with the two
-// exact scalings folded into the constants: v / (den/2) is the same real quotient as
-// 2v / den, and (t * 0.5) * h == t * (0.5 h) because t * 0.5 is exact.  short_div: one
-// Markstein refinement is already correctly rounded for every divisor k/2, k <= 8192
-// (exhaustive over all mantissas: tests/native/divtest.c).
-template <bool SHORT>
-__device__ __forceinline__ float normalise_roundtrip_folded(float v, float dh, float rdh, float half_h) {
-  float q = __fmul_rn(v, rdh);
-  float e = __builtin_fmaf(-dh, q, v);
-  q = __builtin_fmaf(e, rdh, q);
-  if constexpr (!SHORT) {
-    e = __builtin_fmaf(-dh, q, v);
-    q = __builtin_fmaf(e, rdh, q);
-  }
-  const float g = __fsub_rn(q, 1.0f);
-  return __fmul_rn(__fadd_rn(g, 1.0f), half_h);
-}
-// block-uniform choice at run time (the compiler turns it into a select over both results;
-// the hot loops branch once outside instead and call the template)
-__device__ __forceinline__ float normalise_roundtrip_folded(float v, float dh, float rdh, float half_h, bool short_div) {
-  return short_div ? normalise_roundtrip_folded<true>(v, dh, rdh, half_h) : normalise_roundtrip_folded<false>(v, dh, rdh, half_h);
-}
-
-// one control plane of the displacement field for this thread's (j, k) column:
-// the two inner lerps of ATen's upsample_trilinear3d (K innermost, then J)
-__device__ __forceinline__ void cp_plane(const float* __restrict__ cp, int ii, int s_i, int s_j, const Lerp1D& lj,
-                                         const Lerp1D& lk, float (&P)[3]) {
-  const float* p0 = cp + ii * s_i + lj.i0 * s_j;
-  const float* p1 = cp + ii * s_i + lj.i1 * s_j;
-  const int k0 = lk.i0 * 3, k1 = lk.i1 * 3;
-#pragma unroll
-  for (int c = 0; c < 3; c++) {
-    const float a0 = lerp2(p0[k0 + c], lk.l0, p0[k1 + c], lk.l1);
-    const float a1 = lerp2(p1[k0 + c], lk.l0, p1[k1 + c], lk.l1);
-    P[c] = lerp2(a0, lj.l0, a1, lj.l1);
-  }
-}
-
 // dtype access by kernel mode: 0 = float32 only, 1 = float32/int16/uint8/int32, 2 = any
 template <int DTMODE>
 __device__ __forceinline__ float load_mode(const void* p, int dtype, int64_t i) {
@@ -200,14 +164,7 @@ __device__ __forceinline__ void gather_voxel(const ImgArgs& g, const ResampleArg
     const float wx0 = x1 - x, wx1 = x - x0;
     const float wy0 = y1 - y, wy1 = y - y0;
     const float wz0 = z1 - z, wz1 = z - z0;
-    w[0] = __fmul_rn(__fmul_rn(wx0, wy0), wz0);
-    w[1] = __fmul_rn(__fmul_rn(wx1, wy0), wz0);
-    w[2] = __fmul_rn(__fmul_rn(wx0, wy1), wz0);
-    w[3] = __fmul_rn(__fmul_rn(wx1, wy1), wz0);
-    w[4] = __fmul_rn(__fmul_rn(wx0, wy0), wz1);
-    w[5] = __fmul_rn(__fmul_rn(wx1, wy0), wz1);
-    w[6] = __fmul_rn(__fmul_rn(wx0, wy1), wz1);
-    w[7] = __fmul_rn(__fmul_rn(wx1, wy1), wz1);
+    corner_weights(wx0, wx1, wy0, wy1, wz0, wz1, w);
     const bool bx0 = (x0 >= 0.0f) & (x0 <= hx), bx1 = (x1 >= 0.0f) & (x1 <= hx);
     const bool by0 = (y0 >= 0.0f) & (y0 <= hy), by1 = (y1 >= 0.0f) & (y1 <= hy);
     const bool bz0 = (z0 >= 0.0f) & (z0 <= hz), bz1 = (z1 >= 0.0f) & (z1 <= hz);
@@ -513,14 +470,7 @@ __device__ __forceinline__ float tile_mask(const TapSet& ts, float x, float y, f
   const bool oy0 = (y0 >= 0.0f) & (y0 <= hy), oy1 = (y1 >= 0.0f) & (y1 <= hy);
   const bool oz0 = (z0 >= 0.0f) & (z0 <= hz), oz1 = (z1 >= 0.0f) & (z1 <= hz);
   float w[8];
-  w[0] = __fmul_rn(__fmul_rn(ts.wx0, ts.wy0), ts.wz0);
-  w[1] = __fmul_rn(__fmul_rn(ts.wx1, ts.wy0), ts.wz0);
-  w[2] = __fmul_rn(__fmul_rn(ts.wx0, ts.wy1), ts.wz0);
-  w[3] = __fmul_rn(__fmul_rn(ts.wx1, ts.wy1), ts.wz0);
-  w[4] = __fmul_rn(__fmul_rn(ts.wx0, ts.wy0), ts.wz1);
-  w[5] = __fmul_rn(__fmul_rn(ts.wx1, ts.wy0), ts.wz1);
-  w[6] = __fmul_rn(__fmul_rn(ts.wx0, ts.wy1), ts.wz1);
-  w[7] = __fmul_rn(__fmul_rn(ts.wx1, ts.wy1), ts.wz1);
+  corner_weights(ts.wx0, ts.wx1, ts.wy0, ts.wy1, ts.wz0, ts.wz1, w);
   float mask = 0.0f;
 #pragma unroll
   for (int k = 0; k < 8; k++) {
@@ -751,8 +701,6 @@ __global__ __launch_bounds__(TJ* TK, (TJ * TK) / 256 * OCC) void resample_tile_k
                      (m12 == 0.0f) & (m13 == 0.0f) & (m20 == 0.0f) & (m21 == 0.0f) & (m22 == 1.0f) & (m23 == 0.0f);
   // the three block-uniform modes of TIO_FINISH_COORD; the hot elastic loop shadows them with literals
   const bool m_unit = a.unit_spacing != 0, m_ident = ident, m_affine_first = a.affine_first != 0;
-#define TIO_AFFINE_ROW(M0, M1, M2, M3, A, B, C) \
-  __builtin_fmaf(1.0f, M3, __builtin_fmaf(C, M2, __builtin_fmaf(B, M1, __fmul_rn(A, M0))))
 #define TIO_FINISH_COORD(T, DI, DJ, DK, HAS_D, NORM)                                                \
   {                                                                                             \
     float vi, vj, vk;                                                                           \
@@ -916,7 +864,6 @@ __global__ __launch_bounds__(TJ* TK, (TJ * TK) / 256 * OCC) void resample_tile_k
     TIO_TRACK_ALL(t)                                                                                              \
     if ((t & 3) == 3) __builtin_amdgcn_sched_barrier(0);                                                          \
   }
-        // one block-uniform branch instead of a select per division
         // one block-uniform branch instead of a select per division, and - for unit spacing, the usual
         // 1 mm volumes - one copy of the loop per composition order, so that the 16 unrolled planes carry
         // no scalar branches at all (they cost a wave more than the arithmetic they skip)
@@ -979,7 +926,6 @@ __global__ __launch_bounds__(TJ* TK, (TJ * TK) / 256 * OCC) void resample_tile_k
 #undef TIO_NORM_SKIP
 #undef TIO_NORM_SHORT
 #undef TIO_NORM_FULL
-#undef TIO_AFFINE_ROW
 
   // ---- phase B: bounding boxes: whole brick, else halves, else quarters ----------------
   int nsplit = 1;
