@@ -1107,6 +1107,32 @@ int tio_centre_draw(const void* weights, int32_t element_type, int32_t label_mod
 int tio_patch_gather(const void* x, void* y, int32_t element_bytes, int32_t channels, const int32_t shape[3], const int32_t patch[3],
                      const int32_t* corners_dev, int32_t n_patches, void* stream);
 
+/*
+ * NIfTI-1 payloads decoded on the device (additive to ABI 18, HIP only): what a host reader does after reading the bytes
+ * - reinterpret, byte swap, Fortran-to-C reorder, promotion or scaling, conversion - as ONE launch over the raw bytes.
+ *   raw_dev  batch * channels dense volumes of I * J * K disk elements each, back to back, exactly as they lie in the
+ *            file (I fastest, the channel slowest); the first starts on a 16-byte boundary
+ *   y        (batch, channels, I, J, K) contiguous, of out_type:  y[b, c, i, j, k] = raw[b * channels + c][(k * J + j) * I + i]
+ *   values   unscaled: the disk value in its natural type - the disk type itself, except u16 -> int32, u32 -> int64 and
+ *            u64 -> int64 (two's-complement wrap);  scaled: double(x) * slope, rounded, + inter, rounded (no fma): float64
+ *   out_type the natural type (TIO_F64 when scaled), or TIO_F32 / TIO_F64 reached by ONE round-to-nearest-even
+ *            conversion from the exact unscaled value or from the float64 scaled value; anything else:
+ *            TIO_ERR_UNSUPPORTED_DTYPE
+ * disk_type is a NIfTI-1 datatype code: 2 u8, 4 i16, 8 i32, 16 f32, 64 f64, 256 i8, 512 u16, 768 u32, 1024 i64, 1280 u64.
+ * I > 1 and K > 1 go through a 64 x 64 LDS tile (rows read along i, columns written along k); I == 1 or K == 1 (2-D
+ * images) move element by element.  Bad arguments: TIO_ERR_INVALID_ARGUMENT, nothing launched.  raw_dev and y must not
+ * overlap.
+ */
+typedef struct tio_nifti_layout {
+  int32_t disk_type;  /* NIfTI datatype code */
+  int32_t swap_bytes; /* payload is big-endian */
+  int32_t shape[3];   /* I, J, K: on disk I is the fastest axis, in y K is */
+  int32_t channels;
+  int32_t scaled;     /* apply slope / inter (float64 arithmetic, two roundings) */
+  double slope, inter;
+} tio_nifti_layout;
+int tio_nifti_decode(const void* raw_dev, void* y, int32_t out_type, int32_t batch, const tio_nifti_layout* layout, void* stream);
+
 /* ------------------------------------------------------------------------ */
 /* Introspection                                                             */
 /* ------------------------------------------------------------------------ */

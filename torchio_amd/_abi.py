@@ -107,6 +107,20 @@ class ConvPass(C.Structure):
     ]
 
 
+class NiftiLayout(C.Structure):
+    """``tio_nifti_layout`` (host memory)."""
+
+    _fields_ = [
+        ("disk_type", C.c_int32),
+        ("swap_bytes", C.c_int32),
+        ("shape", C.c_int32 * 3),
+        ("channels", C.c_int32),
+        ("scaled", C.c_int32),
+        ("slope", C.c_double),
+        ("inter", C.c_double),
+    ]
+
+
 MAX_PATCHES = 32
 MAX_SEGMENTS = 32  # TIO_MAX_SEGMENTS
 # tio_overlap_mode
@@ -298,6 +312,8 @@ HIP_ONLY_PROTOTYPES = {
          C.c_int64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     ),
     "patch_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _I32x3, _I32x3, C.c_void_p, C.c_int32, C.c_void_p]),
+    # NIfTI-1 payloads decoded on the device (additive to ABI 18): raw bytes in, no CPU restatement either
+    "nifti_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(NiftiLayout), C.c_void_p]),
 }
 CENTRE_SEGMENT = 2048  # TIO_CENTRE_SEGMENT
 CENTRE_MAX_LABELS = 64  # TIO_CENTRE_MAX_LABELS

@@ -7,6 +7,8 @@ from .batch import SubjectsBatch
 from .image import Image
 from .image import LabelMap
 from .image import ScalarImage
+from .image import read_image
+from .nifti import write_nifti
 from .patch import PatchLocation
 from .points import Points
 from .queue import Queue
@@ -22,4 +24,5 @@ from .subject import Subject
 __all__ = [
     "AffineMatrix", "BoundingBoxFormat", "BoundingBoxes", "GridSampler", "Image", "ImagesBatch", "LabelMap", "LabelSampler", "PatchAggregator", "PatchLocation",
     "PatchSampler", "Points", "Queue", "ScalarImage", "Subject", "SubjectsBatch", "UniformSampler", "WeightedSampler", "get_centre_draw", "set_centre_draw",
+    "read_image", "write_nifti",
 ]

@@ -16,6 +16,7 @@ from torch import Tensor
 
 from . import _lazy
 from . import _pending
+from . import nifti as _nifti
 from .affine import AffineMatrix
 from .image import Image
 from .image import ScalarImage
@@ -159,15 +160,24 @@ class SubjectsBatch(_History):
         self.bounding_boxes: list[dict] | None = None
 
     @classmethod
-    def from_subjects(cls, subjects: list[Any], *, data: dict[str, Tensor] | None = None) -> "SubjectsBatch":
-        """*data*: already stacked ``(B, C, I, J, K)`` voxels per image name (see ``ImagesBatch.from_images``)."""
+    def from_subjects(cls, subjects: list[Any], *, data: dict[str, Tensor] | None = None, device=None) -> "SubjectsBatch":
+        """*data*: already stacked ``(B, C, I, J, K)`` voxels per image name (see ``ImagesBatch.from_images``).
+
+        *device*: where the batch is wanted.  On a cuda device, the unloaded file-backed images under one name that share
+        shape, disk type, endianness and scaling are read in one step: the payloads in ONE pinned buffer, one H2D copy and
+        ONE ``tio_nifti_decode`` writing the stacked tensor (no per-image tensor, no ``torch.stack``; the images stay
+        unloaded).  Any other group is loaded image by image on *device* and stacked.  ``None``: the voxels stay where the
+        images have them."""
         if not subjects:
             raise ValueError("Cannot create batch from empty list")
         first = subjects[0]
-        images = {
-            name: ImagesBatch.from_images([subject.images[name] for subject in subjects], data=None if data is None else data.get(name))
-            for name in first.images
-        }
+        images = {}
+        for name in first.images:
+            group = [subject.images[name] for subject in subjects]
+            stacked = None if data is None else data.get(name)
+            if stacked is None and device is not None:
+                stacked = _stack_on_device(group, torch.device(device))
+            images[name] = ImagesBatch.from_images(group, data=stacked)
         metadata = {key: [subject.metadata[key] for subject in subjects] for key in first.metadata}
         new = cls(images, metadata=metadata)
         if any(subject._points for subject in subjects):
@@ -284,6 +294,16 @@ class SubjectsBatch(_History):
 
     def __repr__(self) -> str:
         return f"SubjectsBatch(batch_size={self.batch_size}, images=[{', '.join(self._images)}])"
+
+
+def _stack_on_device(images: list[Image], device: torch.device) -> Tensor:
+    """The stacked voxels of *images* on *device* (``SubjectsBatch.from_subjects(device=...)``)."""
+    headers = [image._header for image in images]
+    lazy = device.type == "cuda" and all(header is not None and not image.is_loaded for header, image in zip(headers, images, strict=True))
+    if lazy and len({header.group_key() for header in headers}) == 1 and len({image._destination[1] for image in images}) == 1:
+        return _nifti.read_stacked(headers, device, images[0]._destination[1])
+    # (an unloaded image is decoded on the device and keeps its voxels there; a loaded one stays where it is)
+    return torch.stack([(image if image.is_loaded else image.load(device)).data.to(device) for image in images])
 
 
 def _move_annotations(stores, args, kwargs) -> None:

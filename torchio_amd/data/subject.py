@@ -110,7 +110,15 @@ class Subject:
             entry.to(*args, **kwargs)
         return self
 
-    def load(self) -> "Subject":
+    @property
+    def shape(self) -> tuple[int, int, int, int]:
+        """``(C, I, J, K)`` of the first image (from the header alone for an unloaded file-backed image)."""
+        return next(iter(self._images.values())).shape
+
+    def load(self, device=None) -> "Subject":
+        """Read every file-backed image now (on *device* when given; tensor-backed images are moved there too)."""
+        for image in self._images.values():
+            image.load(device)
         return self
 
     # -- history -------------------------------------------------------------

@@ -1771,6 +1771,36 @@ class Engine:
                    corners.shape[0], self._stream(data))
         return out
 
+    def nifti_decode(self, raw: Tensor, *, disk_type: int, shape: Sequence[int], channels: int = 1, batch: int = 1, swap_bytes: bool = False,
+                     slope: float | None = None, inter: float = 0.0, out_dtype: torch.dtype | None = None) -> Tensor:
+        """The payloads of ``batch`` NIfTI-1 files, as bytes on the device, to one ``(batch, channels, I, J, K)`` tensor in
+        ONE launch (``tio_nifti_decode``): byte swap, Fortran-to-C reorder, promotion or scaling and conversion.
+
+        ``raw``: uint8, ``batch * channels`` dense volumes of ``I * J * K`` elements of ``disk_type`` (a NIfTI datatype
+        code) back to back, 16-byte aligned.  ``slope``: ``None`` for an unscaled read, else ``float64(x) * slope + inter``
+        with two roundings.  ``out_dtype``: the natural dtype (default; float64 when scaled), or float32 / float64 reached
+        in one rounding.
+        """
+        from .data.nifti import DATATYPES  # noqa: PLC0415
+
+        if disk_type not in DATATYPES:
+            raise ValueError(f"nifti_decode: datatype {disk_type} is not supported (supported: {sorted(DATATYPES)})")
+        shape = [int(s) for s in shape]
+        if len(shape) != 3 or min(shape) < 1 or channels < 1 or batch < 1:
+            raise ValueError(f"nifti_decode: shape {tuple(shape)}, channels {channels} and batch {batch} must be positive")
+        scaled = slope is not None
+        natural = torch.float64 if scaled else DATATYPES[disk_type][2]
+        out_dtype = natural if out_dtype is None else out_dtype
+        needed = batch * channels * shape[0] * shape[1] * shape[2] * DATATYPES[disk_type][1]
+        if raw.dtype != torch.uint8 or raw.ndim != 1 or not raw.is_contiguous() or raw.numel() < needed:
+            raise ValueError(f"nifti_decode: raw must be a contiguous 1-D uint8 tensor of at least {needed} bytes, got {raw.dtype} {tuple(raw.shape)}")
+        self._check("nifti_decode", raw)
+        layout = _abi.NiftiLayout(disk_type=int(disk_type), swap_bytes=int(bool(swap_bytes)), shape=_i32x3(shape), channels=int(channels),
+                                  scaled=int(scaled), slope=float(slope) if scaled else 1.0, inter=float(inter) if scaled else 0.0)
+        out = torch.empty((batch, channels, *shape), dtype=out_dtype, device=raw.device)
+        self._call("nifti_decode", raw, _ptr(raw), _ptr(out), dtype_code(out_dtype), batch, C.byref(layout), self._stream(raw))
+        return out
+
 
 class CentreDraw(NamedTuple):
     """What :meth:`Engine.centre_draw` leaves on the device."""

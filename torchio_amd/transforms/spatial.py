@@ -21,6 +21,7 @@ Not implemented on the engine (raise, never fall back): interpolation orders
 from __future__ import annotations
 
 import math
+import os
 import warnings
 from dataclasses import dataclass
 from numbers import Number
@@ -34,6 +35,7 @@ from torch.distributions import Distribution
 
 from .. import ops
 from .. import streams
+from ..data import nifti as _nifti
 from ..data.affine import AffineMatrix
 from ..data.batch import ImagesBatch
 from ..data.batch import SubjectsBatch
@@ -1414,9 +1416,12 @@ def _resolve_target_space(target, batch: SubjectsBatch, first_shape, first_affin
         if isinstance(target, str) and target in batch.images:
             reference = batch.images[target]
             return _spatial_shape(reference), reference.affines[0].clone()
+        if _nifti.is_nifti_path(target) and os.path.isfile(target):  # a NIfTI file: its header alone holds the target space
+            header = _nifti.read_header(target)
+            return header.shape, AffineMatrix(header.affine)
         raise ValueError(
             f'Unknown target "{target}". Pass an image name in the subject, an Image, a (shape, affine) pair'
-            " or a spacing specification (reading a target image from a file path is not supported here)"
+            " or a spacing specification (a file path must be an existing .nii or .nii.gz file)"
         )
     if _is_target_space_tuple(target):
         return _parse_target_space_tuple(*target)
