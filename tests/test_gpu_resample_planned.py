@@ -22,10 +22,33 @@ def _rel(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return (a.double() - b.double()).abs() / a.double().abs().clamp_min(1.0)
 
 
+def starts_from_a_plan(hip, images, *, precision, out_shape, mapping, control_points, large_boxes=0, **geometry) -> bool:
+    """Does the float group of this launch take a PLANNED road under the switches in force?  (`tio_resample3d_plan_bytes`
+    behind `resample_plan`: the question `choose_float_road` answers for the call.)  A switch such as TIO_FAST_KERNEL=planned
+    asks for the road; the geometry can still refuse it — control cells narrower than a brick, K not a multiple of 4 — and
+    the launch then falls back to a single-kernel road.  `geometry`: the other keyword arguments of the `resample3d` call."""
+    data = images[0]
+    plan = hip.resample_plan(
+        batch=data.shape[0], in_shape=tuple(data.shape[2:]), out_shape=out_shape, mapping=mapping, control_points=control_points,
+        in_spacing=geometry["in_spacing"], out_spacing=geometry["out_spacing"], affine_first=geometry["affine_first"],
+        cp_skip=geometry.get("cp_skip"), passthrough=geometry.get("passthrough"), precision=precision, large_boxes=large_boxes,
+    )
+    return plan is not None
+
+
+def control_cells_span_a_brick(shape, grid) -> bool:
+    """The planner's condition on an elastic launch, restated: along every axis with more than two control points a control
+    cell is at least 16 voxels wide, `(n_vox - 1) >= 16 (n_ctl - 1)` (resample.hip: choose_float_road)."""
+    return all(n_ctl <= 2 or (n_vox - 1) >= 16 * (n_ctl - 1) for n_vox, n_ctl in zip(shape, grid))
+
+
 @pytest.mark.parametrize("elastic", [False, True])
 @pytest.mark.parametrize("with_fill", [False, True])
-@pytest.mark.parametrize("shape", [(64, 64, 64), (70, 52, 56)])
+@pytest.mark.parametrize("shape", [(64, 64, 64), (70, 52, 56), (68, 72, 80)])
 def test_planned_fast_bricks_stay_within_tolerance(hip, monkeypatch, elastic, with_fill, shape):
+    """Affine launches of all three shapes, and the elastic launch of 68 x 72 x 80, run the planned kernels.  The 5^3 control
+    grid on 64^3 and on 70 x 52 x 56 has cells narrower than a brick (63 < 64, 51 < 64): under TIO_FAST_KERNEL=planned those
+    two elastic launches are the FALLBACK to the brick kernel's FAST instantiation — kept, and held to the same tolerance."""
     batch = 3
     g = torch.Generator(device="cuda").manual_seed(5)
     t1 = torch.rand(batch, 1, *shape, generator=g, device="cuda") * 4 - 1
@@ -41,6 +64,9 @@ def test_planned_fast_bricks_stay_within_tolerance(hip, monkeypatch, elastic, wi
     brick = hip.resample3d([t1, t2], precision="fast", **kwargs)
     monkeypatch.setenv("TIO_FAST_KERNEL", "planned")
     planned = hip.resample3d([t1, t2], precision="fast", **kwargs)
+    on_planned_road = starts_from_a_plan(hip, [t1, t2], precision="fast", **kwargs)
+    assert on_planned_road == (not elastic or control_cells_span_a_brick(shape, (5, 5, 5)))
+    assert on_planned_road == (not elastic or shape == (68, 72, 80))
     torch.cuda.synchronize()
     for e, b, p in zip(exact, brick, planned):
         assert not torch.equal(e, p)
@@ -65,6 +91,7 @@ def test_planned_fast_bricks_handle_gated_and_far_away_elements(hip, monkeypatch
     exact = hip.resample3d([data], precision="exact", **kwargs)[0]
     monkeypatch.setenv("TIO_FAST_KERNEL", "planned")
     planned = hip.resample3d([data], precision="fast", **kwargs)[0]
+    assert starts_from_a_plan(hip, [data], precision="fast", **kwargs)
     torch.cuda.synchronize()
     assert torch.equal(planned[1], data[1])
     assert torch.all(planned[2] == -3.0) and torch.all(exact[2] == -3.0)
@@ -98,6 +125,7 @@ def test_fast_fill_decisions_are_the_exact_kernels(hip, monkeypatch, elastic, ro
     exact = hip.resample3d([data], precision="exact", **kwargs)[0]
     monkeypatch.setenv("TIO_FAST_KERNEL", "brick" if road == "brick" else "planned")
     fast = hip.resample3d([data], precision="fast", **kwargs)[0]
+    assert starts_from_a_plan(hip, [data], precision="fast", **kwargs) == (road != "brick")
     torch.cuda.synchronize()
     filled_exact, filled_fast = exact == FILL, fast == FILL
     assert int(filled_exact.sum()) > 10_000  # part of the field of view does leave the volume
@@ -130,6 +158,7 @@ def test_fast_fill_decisions_on_a_plane_that_sits_on_the_threshold(hip, monkeypa
     for road in ("planned", "brick"):
         monkeypatch.setenv("TIO_FAST_KERNEL", road)
         fast = hip.resample3d([data], precision="fast", **kwargs)[0]
+        assert starts_from_a_plan(hip, [data], precision="fast", **kwargs) == (road == "planned")
         torch.cuda.synchronize()
         assert int(((exact == FILL) != (fast == FILL)).sum()) == 0, road
         assert float(_rel(exact, fast).max()) <= REL_TOL, road
@@ -143,6 +172,7 @@ def test_fast_fill_decisions_without_the_recheck_do_flip(hip, monkeypatch):
     monkeypatch.setenv("TIO_FAST_KERNEL", "planned")
     monkeypatch.setenv("TIO_FAST_FILL_RECHECK", "0")
     fast = hip.resample3d([data], precision="fast", **kwargs)[0]
+    assert starts_from_a_plan(hip, [data], precision="fast", **kwargs)
     torch.cuda.synchronize()
     flipped = int(((exact == FILL) != (fast == FILL)).sum())
     assert flipped > 0, "no voxel within rounding of the threshold: the comparisons above would prove nothing"
@@ -163,6 +193,7 @@ def test_fast_fill_decisions_on_the_per_voxel_road(hip, monkeypatch):
     for road in ("planned", "brick"):
         monkeypatch.setenv("TIO_FAST_KERNEL", road)
         fast = hip.resample3d([data], precision="fast", **kwargs)[0]
+        assert starts_from_a_plan(hip, [data], precision="fast", **kwargs) == (road == "planned")
         torch.cuda.synchronize()
         assert int(((exact == FILL) != (fast == FILL)).sum()) == 0, road
         assert float(_rel(exact, fast).max()) <= REL_TOL, road
@@ -184,6 +215,7 @@ def test_lean_kernel_divides_brick_indices_exactly_beyond_2_32(hip, monkeypatch)
                   affine_first=True, interps=["linear"], fills=[None])
     monkeypatch.setenv("TIO_FAST_KERNEL", "planned")
     fast = hip.resample3d([data], precision="fast", **kwargs)[0]
+    assert starts_from_a_plan(hip, [data], precision="fast", **kwargs)
     torch.cuda.synchronize()
     exact = hip.resample3d([data], precision="exact", **kwargs)[0]
     torch.cuda.synchronize()
@@ -208,6 +240,7 @@ def test_planned_fast_bricks_with_boxes_beyond_the_lds_budget(hip, monkeypatch):
     exact = hip.resample3d([data], precision="exact", **kwargs)[0]
     monkeypatch.setenv("TIO_FAST_KERNEL", "planned")
     planned = hip.resample3d([data], precision="fast", **kwargs)[0]
+    assert starts_from_a_plan(hip, [data], precision="fast", **kwargs)
     torch.cuda.synchronize()
     assert float(_rel(exact, planned).max()) <= REL_TOL
 
@@ -228,6 +261,7 @@ def test_planned_exact_affine_launches_are_bit_identical(hip, monkeypatch, shape
     plain = hip.resample3d([t1, seg], **kwargs)
     monkeypatch.setenv("TIO_EXACT_PLAN", "2")
     planned = hip.resample3d([t1, seg], **kwargs)
+    assert starts_from_a_plan(hip, [t1, seg], **kwargs)  # (the float group: the label map has its own kernel)
     torch.cuda.synchronize()
     assert torch.equal(plain[0], planned[0]) and torch.equal(plain[1], planned[1])
 
@@ -314,13 +348,11 @@ def test_compose_is_bit_identical_with_and_without_the_folded_minimum(hip, monke
     assert torch.equal(results[0], results[1])
 
 
-def test_two_host_threads_share_a_stream_without_sharing_a_plan(hip, monkeypatch):
-    """VERDICT r2 weak #9 / ADVICE r2: a planned launch is plan_bricks_kernel + the sampling kernel; two host threads on the
-    SAME stream (the reference's Queue workers, data/queue.py:119-123) must never interleave planA, planB, sampleA.
-    Different mappings per thread, many rounds, both the FAST planned bricks and the planned exact affine launches;
-    every result equals the one the same call gives when issued alone."""
-    import threading
-
+def two_thread_jobs(hip, monkeypatch):
+    """The data and the eight jobs `(keyword arguments, precision)` of the two-thread tests (this one, and the held stream of
+    test_gpu_stream_order.py) under their switches — every one of them a PAIR of kernels, planner + sampler, which is
+    asserted: the FAST planned bricks, and for the exact jobs the exact-coordinate lean kernel (TIO_FAST_KERNEL=planned forces that one as well, affine
+    or elastic; TIO_EXACT_PLAN=2 plans the brick kernel's affine launch wherever the lean kernel does not take it)."""
     monkeypatch.setenv("TIO_FAST_KERNEL", "planned")
     monkeypatch.setenv("TIO_EXACT_PLAN", "2")
     batch, shape = 2, (96, 96, 96)
@@ -335,6 +367,19 @@ def test_two_host_threads_share_a_stream_without_sharing_a_plan(hip, monkeypatch
         )
 
     jobs = [(kwargs(100 + 7 * n, n % 3 == 0), "fast" if n % 2 == 0 else "exact") for n in range(8)]
+    for kw, p in jobs:
+        assert starts_from_a_plan(hip, [data], precision=p, **kw), (p, kw["control_points"] is not None)
+    return data, jobs
+
+
+def test_two_host_threads_share_a_stream_without_sharing_a_plan(hip, monkeypatch):
+    """VERDICT r2 weak #9 / ADVICE r2: a planned launch is plan_bricks_kernel + the sampling kernel; two host threads on the
+    SAME stream (the reference's Queue workers, data/queue.py:119-123) must never interleave planA, planB, sampleA.
+    Different mappings per thread, many rounds, both the FAST planned bricks and the planned exact affine launches;
+    every result equals the one the same call gives when issued alone."""
+    import threading
+
+    data, jobs = two_thread_jobs(hip, monkeypatch)
     serial = [hip.resample3d([data], precision=p, **kw)[0] for kw, p in jobs]
     torch.cuda.synchronize()
     stream = torch.cuda.current_stream()
@@ -359,12 +404,9 @@ def test_two_host_threads_share_a_stream_without_sharing_a_plan(hip, monkeypatch
     assert not failures, failures
 
 
-@pytest.mark.parametrize("seed", range(16))
-def test_fast_fill_decisions_fuzz(hip, monkeypatch, seed):
-    """Random geometries far from the bench's (zooms 0.5 - 2, rotations up to +-40 degrees, shifts, anisotropic spacings, both
-    composition orders, control grids of several densities and amplitudes, ragged shapes): on every FAST road the fill decision
-    of every voxel is the exact kernel's, and kept values stay within the tolerance (smooth data: the bar is about the
-    arithmetic, not about white noise amplifying a coordinate's last bits)."""
+def _fuzz_fill_decisions(hip, monkeypatch, seed, extent_ij, quads_k):
+    """One random geometry (extents of I and J drawn from `extent_ij`, K four times a draw from `quads_k`) on both FAST roads;
+    returns (elastic, shape, grid, did TIO_FAST_KERNEL=planned start from a plan)."""
     import math
 
     g = torch.Generator().manual_seed(1000 + seed)
@@ -373,7 +415,7 @@ def test_fast_fill_decisions_fuzz(hip, monkeypatch, seed):
         return lo + (hi - lo) * float(torch.rand(1, generator=g))
 
     batch = 2 + seed % 2
-    shape = tuple(int(rnd(40, 97)) for _ in range(2)) + (4 * int(rnd(10, 25)),)
+    shape = tuple(int(rnd(*extent_ij)) for _ in range(2)) + (4 * int(rnd(*quads_k)),)
     axes = [torch.arange(s, dtype=torch.float32) / s for s in shape]
     volume = 0.5 + 0.25 * torch.sin(6.0 * axes[0])[:, None, None] + 0.2 * torch.cos(5.0 * axes[1])[None, :, None] + 0.3 * axes[2][None, None, :]
     data = torch.stack([volume + 0.1 * b for b in range(batch)])[:, None].contiguous().cuda()
@@ -401,11 +443,43 @@ def test_fast_fill_decisions_fuzz(hip, monkeypatch, seed):
     )
     exact = hip.resample3d([data], precision="exact", **kwargs)[0]
     filled = exact == FILL
+    planned = None
     for road in ("planned", "brick"):
         monkeypatch.setenv("TIO_FAST_KERNEL", road)
         monkeypatch.setenv("TIO_PLANNED_LEAN", "1" if seed % 2 else "0")
         fast = hip.resample3d([data], precision="fast", **kwargs)[0]
+        if road == "planned":
+            planned = starts_from_a_plan(hip, [data], precision="fast", **kwargs)
+        else:
+            assert not starts_from_a_plan(hip, [data], precision="fast", **kwargs)
         torch.cuda.synchronize()
         flips = int((filled != (fast == FILL)).sum())
         assert flips == 0, (road, flips, shape, elastic)
         assert float(_rel(exact, fast).max()) <= REL_TOL, (road, float(_rel(exact, fast).max()))
+    return elastic, shape, grid, planned
+
+
+@pytest.mark.parametrize("seed", range(16))
+def test_fast_fill_decisions_fuzz(hip, monkeypatch, seed):
+    """Random geometries far from the bench's (zooms 0.5 - 2, rotations up to +-40 degrees, shifts, anisotropic spacings, both
+    composition orders, control grids of several densities and amplitudes, ragged shapes): on every FAST road the fill decision
+    of every voxel is the exact kernel's, and kept values stay within the tolerance (smooth data: the bar is about the
+    arithmetic, not about white noise amplifying a coordinate's last bits).
+
+    Which roads these are: the affine seeds (every third) run the planned kernels under TIO_FAST_KERNEL=planned; the elastic
+    seeds all draw extents below 97 with grids of (5, 6, 7) or 7^3 control points — cells narrower than a brick along K at
+    the least — so their "planned" pass is the FALLBACK to the brick kernel's FAST instantiation, twice.  The elastic planned
+    kernels meet the same fuzz in `test_fast_fill_decisions_fuzz_on_the_elastic_planned_road`."""
+    elastic, shape, grid, planned = _fuzz_fill_decisions(hip, monkeypatch, seed, (40, 97), (10, 25))
+    assert planned == (not elastic), (shape, grid)
+    assert planned == (not elastic or control_cells_span_a_brick(shape, grid)), (shape, grid)
+
+
+@pytest.mark.parametrize("seed", [1, 2, 4, 5, 7, 8])
+def test_fast_fill_decisions_fuzz_on_the_elastic_planned_road(hip, monkeypatch, seed):
+    """The elastic geometries of the fuzz above at extents of 100 - 130 voxels (K a multiple of 4), where a cell of the
+    (5, 6, 7) and 7^3 grids is at least a brick wide: TIO_FAST_KERNEL=planned really starts from a plan — the general planned
+    kernel on even seeds, the lean one on odd seeds; anisotropic spacing on seed 5 — and is held to the same two bars."""
+    elastic, shape, grid, planned = _fuzz_fill_decisions(hip, monkeypatch, seed, (100, 131), (25, 33))
+    assert elastic and control_cells_span_a_brick(shape, grid), (shape, grid)
+    assert planned, (shape, grid)

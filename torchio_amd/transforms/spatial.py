@@ -1049,11 +1049,19 @@ _EYE34 = np.eye(3, 4, dtype=np.float32)
 
 
 def _identity_mapping(device) -> Tensor:
-    """The shared ``(1, 3, 4)`` identity mapping, uploaded once per device (read-only)."""
+    """The shared ``(1, 3, 4)`` identity mapping, uploaded once per device (read-only).
+
+    Every stream and thread reads the ONE tensor, whichever stream was current when the first caller asked — `_prefetch`
+    asks on the ahead stream, and only that caller's launch is ordered behind it (`Ahead.join`).  So the upload is finished,
+    on the host's word, before the tensor enters the cache: a launch on any other stream finds it written.  (A stream-ordered
+    `h2d` here left the next reader on another stream — a second thread, a caller who changed streams — racing the copy.)"""
     key = str(device)
     mapping = _IDENTITY_MAPPINGS.get(key)
     if mapping is None:
-        mapping = _IDENTITY_MAPPINGS[key] = ops.h2d(torch.eye(3, 4, dtype=torch.float32)[None].contiguous(), device)
+        mapping = torch.eye(3, 4, dtype=torch.float32)[None].contiguous().to(device)
+        if mapping.is_cuda:
+            torch.cuda.current_stream(mapping.device).synchronize()
+        _IDENTITY_MAPPINGS[key] = mapping
     return mapping
 
 
