@@ -1144,6 +1144,11 @@ int tio_device_count(void);
  * ONCE, at the first call that needs one; no entry point calls getenv() afterwards.  A process that changes such a
  * variable later (tests, tests/native/resample_bench) calls this to have them parsed again.  ABI 10. */
 void tio_reload_env(void);
+/* The cache policy a launch that writes `bytes_written` bytes takes (host only, nothing is launched): 1 = "stream" — its
+ * once-touched rows bypass the caches' retention (nontemporal loads and stores: the marching stencil passes of
+ * tio_separable_conv3d / tio_blur_fused), 0 = the default policy.  A launch streams when it writes more than the Infinity Cache holds
+ * (256 MiB), or more than TIO_STREAM_BYTES when that is set (0: every launch streams).  Results do not depend on it. */
+int tio_launch_streams(int64_t bytes_written);
 
 #ifdef __cplusplus
 }

@@ -4,6 +4,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <atomic>
 #include <mutex>
 
@@ -59,6 +60,7 @@ static const EnvSwitches* parse_env() {
   e->fast_fill_recheck = num("TIO_FAST_FILL_RECHECK", 1) != 0;
   e->conv_no_fuse = getenv("TIO_CONV_NO_FUSE") != nullptr;
   e->conv_ring = getenv("TIO_CONV_RING") != nullptr;
+  if (const char* v = getenv("TIO_STREAM_BYTES")) e->stream_bytes = std::max<long long>(0, atoll(v));
   return e;
 }
 
@@ -77,6 +79,8 @@ extern "C" void tio_reload_env(void) {
   std::lock_guard<std::mutex> lock(tio::g_env_mu);
   tio::g_env.store(tio::parse_env(), std::memory_order_release);
 }
+
+extern "C" int tio_launch_streams(int64_t bytes_written) { return tio::launch_streams(bytes_written) ? 1 : 0; }
 
 extern "C" int tio_abi_version(void) { return TIO_ABI_VERSION; }
 

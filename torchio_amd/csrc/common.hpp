@@ -43,8 +43,23 @@ struct EnvSwitches {
   int fast_fill_recheck = 1;     // TIO_FAST_FILL_RECHECK (0: the FAST fill rule decides alone, A/B)
   int conv_no_fuse = 0;          // TIO_CONV_NO_FUSE set
   int conv_ring = 0;             // TIO_CONV_RING set
+  int64_t stream_bytes = -1;     // TIO_STREAM_BYTES: -1 unset (kStreamBytes), else the threshold of launch_streams in bytes (0: every launch streams; huge: none)
 };
 const EnvSwitches& env_switches();
+
+// ---- cache policy of a launch ("stream") --------------------------------------------------------------------------
+// A launch that writes more than the Infinity Cache holds (256 MB on this chip, 4 MB of L2 per XCD: MI355X_MICROARCH.md, memory
+// hierarchy) writes bytes that no consumer will find in a cache: by the time the next launch reads them, at least as much
+// other traffic has gone by.  Such a launch takes the kernels whose once-touched rows carry the nontemporal policy (the guide's
+// rows nt-weights / ldsdma-fill: a once-read stream is faster with `nt` when the caches are cold, slower where a consumer
+// would have hit — hence a threshold per launch and not a global switch).  Below it, the launch is the one it was before the
+// policy existed, instruction for instruction.  Today's users: the marching stencil passes (stencil_march.hpp); the resampler's
+// output stores were measured with it and lost (profiles/cache_policy.md).
+constexpr int64_t kStreamBytes = 256ll << 20;
+inline bool launch_streams(int64_t bytes_written) {
+  const int64_t threshold = env_switches().stream_bytes;
+  return bytes_written > (threshold >= 0 ? threshold : kStreamBytes);
+}
 
 // ---- element type conversion: `.float()` on load, `.to(dtype)` on store -------
 __device__ __forceinline__ float bf16_bits_to_float(uint16_t h) {

@@ -87,6 +87,8 @@ struct BoxDmaStepper {
   template <bool INTERIOR>
   __device__ __forceinline__ void issue(int lane) {
     const bool in_box = lane_ok & (row < total_rows);
+    // (default cache policy, on purpose: neighbouring bricks' boxes overlap — a box is 2.3 x its brick — and the second reader finds
+    // those lines in L2.  The same holds for descriptors, mappings and control points.)
     if constexpr (INTERIOR) {
       if (in_box) __builtin_amdgcn_global_load_lds(origin + off, (fast_lds_wptr)(lp), 16, 0, 0);
     } else {
@@ -343,6 +345,10 @@ __device__ __forceinline__ void lean_exact_group_store(const float (&vals)[4], c
   for (int u = 0; u < 4; u++) {
     const bool live = !GUARD || (col_active && (t0 + u) < i_count);
     if (live) {
+      // (default cache policy.  Nontemporal stores here — to keep the output stream out of the L2 that serves the boxes' overlaps — were
+      // built and measured at the bench shape: the elastic launch +13 us, the affine launch +23 us, five alternations on one box, and
+      // WRITE_SIZE +23 % / +15 % at fetched bytes down by under 1 % — a wave stores 64-byte row segments, and L2 is where they
+      // become whole lines; profiles/cache_policy.md.)
       *(global_float_ptr)(out_t + row_off) = vals[u];
       if constexpr (TRACK) kmin = min(kmin, float_to_key(vals[u]));
     }

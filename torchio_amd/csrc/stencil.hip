@@ -683,14 +683,17 @@ static int launch_conv(const void* x, void* y, float* tmp0, float* tmp1, int32_t
       case TIO_CONV_MARCH: {
         a.bcs = batch * channels;
         a.fma = p.fma;
+        // cache policy of this pass (common.hpp: launch_streams): a marching pass writes every float32 voxel of the batch once
+        const bool streams = launch_streams(static_cast<int64_t>(a.bcs) * shape[0] * shape[1] * shape[2] * static_cast<int64_t>(sizeof(float)));
         if (fused) {  // the fused J + K instantiations are built in a translation unit of their own (stencil_fused.hip)
-          launch_conv_march_fused(p.radius_class, p.post_noise, p.fma != 0, grid, lds, stream, a);
+          launch_conv_march_fused(p.radius_class, p.post_noise, p.fma != 0, streams, grid, lds, stream, a);
           break;
         }
         with_march_radius(p.radius_class, [&](auto radius_tag) {
           with_bools([&](auto bias, auto fm) {
-            hipLaunchKernelGGL((conv_march_kernel<decltype(radius_tag)::value, false, decltype(bias)::value, 0, decltype(fm)::value>), grid,
-                               dim3(kBlock), lds, stream, a);
+            constexpr int R = decltype(radius_tag)::value;
+            if (streams) hipLaunchKernelGGL((conv_stream_march_kernel<R, false, decltype(bias)::value, 0, decltype(fm)::value>), grid, dim3(kBlock), lds, stream, a);
+            else hipLaunchKernelGGL((conv_march_kernel<R, false, decltype(bias)::value, 0, decltype(fm)::value>), grid, dim3(kBlock), lds, stream, a);
           }, pre_bias, p.fma != 0);
         });
         break;
