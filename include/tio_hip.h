@@ -131,6 +131,8 @@ typedef enum tio_interp {
  *   ATen grid_sampler un-normalise  ((g + 1) / 2) * (S - 1)
  *   per-instance variant            spatial.py:1881-1918   (B matrices / fields, no
  *                                                           (B,I,J,K,3) stack)
+ *   grid_sample under autograd      spatial.py:1695-1731   (the grid's gradient, chained to the mapping and
+ *                                                           the control points: tio_resample3d_geometry_grad)
  */
 typedef struct tio_resample_geom {
   int32_t batch;        /* B                                                     */
@@ -256,6 +258,40 @@ int tio_resample3d_plan(const tio_resample_geom* geom, void* plan_dev, int64_t p
 /* Resample n_images image tensors through ONE coordinate computation. */
 int tio_resample3d(const tio_resample_geom* geom, int32_t n_images,
                    const tio_resample_image* images, void* stream);
+
+/*
+ * The gradient of a trilinear resampling with respect to its GEOMETRY: the mapping and the control points (additive to ABI 18,
+ * HIP only).  Replaces what autograd derives through the materialised (B, I, J, K, 3) grid of the reference:
+ *   _sample_batch_grid_sample       spatial.py:1695-1731   (F.grid_sample under autograd: grid_sampler_3d_backward's grad_grid,
+ *                                                           chained back through the grid's construction)
+ * One fused launch forms dL/d(coordinate) per output voxel from the incoming gradients and the eight taps and reduces it straight
+ * into 12 numbers per mapping and ni * nj * nk * 3 per control grid; no per-voxel gradient field reaches memory.
+ *   images[n].in    x_n (B, C_n, I, J, K), one of the four float dtypes (others: TIO_ERR_UNSUPPORTED_DTYPE)
+ *   images[n].out   g_n (B, C_n, Io, Jo, Ko) float32 = dL/d(output of the forward), READ
+ *   images[n].interp  TIO_LINEAR (anything else: TIO_ERR_INVALID_ARGUMENT); fill_dev as in the forward; the label fields and
+ *                   out_min_dev are ignored
+ * With the forward's own float32 sampling coordinate of output voxel o = (i, j, k) of element b (the TIO_PRECISION_EXACT chain,
+ * whatever geom->precision says, as for TIO_LINEAR_ADJOINT), cell = floor(coordinate):
+ *   D_a(o) = sum_n sum_c g_n[b,c,o] * sum_{taps t in bounds} x_n[b,c,t] * s_a(t) * (product of the two other axes' weights of t),
+ *            s_a = -1 on the lower tap and +1 on the upper (ATen's grid_sampler_3d_backward, padding_mode="zeros",
+ *            align_corners=True); where fill_dev of image n is non-NULL and the in-bounds weight is <= 0.5 the forward wrote
+ *            the fill and image n adds nothing at o;
+ *   d_a    = D_a * (S_own[a] - 1) / max(S_norm[a] - 1, 1)   (the normalise / un-normalise round trip; exactly 0 where S_own[a] == 1);
+ *   affine_first == 1, or no elastic component:   dM[r][0..3] += d_r * (i, j, k, 1),        dDisp[e] = d_e / in_spacing[e];
+ *   affine_first == 0 with an elastic component, s = c + disp / out_spacing:
+ *                                                 dM[r][0..3] += d_r * (s_0, s_1, s_2, 1),  dDisp[e] = (sum_r M[r][e] d_r) / out_spacing[e];
+ *   dCP[node][e] += W(node; i, j, k) * dDisp[e] over the eight nodes of the voxel's control cell, W the align-corners lerp weights
+ *            of the forward.
+ * An element with passthrough[b] adds nothing; one with cp_skip[b] adds nothing to dCP, its mapping still receives a gradient.
+ * d_mapping: float32 (B | 1, 3, 4) as mapping_batched says, d_control_points: float32 in the shape of the control points; shared
+ * parameters receive the sum over the batch.  Both are fully overwritten.  Either may be NULL (not wanted; d_control_points must
+ * be NULL when the geometry has no control points), not both.  workspace: tio_resample3d_geometry_grad_workspace_bytes(geom) bytes,
+ * 8-byte aligned, on the device; its contents on entry do not matter.  Sums across blocks are float64 hardware atomics: two runs
+ * differ at most in the last float32 rounding of an output.  plan_dev, precision and flags of the geometry are ignored.
+ */
+int64_t tio_resample3d_geometry_grad_workspace_bytes(const tio_resample_geom* geom);
+int tio_resample3d_geometry_grad(const tio_resample_geom* geom, int32_t n_images, const tio_resample_image* images, float* d_mapping,
+                                 float* d_control_points, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* Per-channel minimum of the FIRST batch element, kept on the device (the
  * reference's default_pad_value="minimum": spatial.py:2054-2060,2094-2095 —

@@ -29,6 +29,7 @@ from .data import get_centre_draw
 from .data import read_image
 from .data import write_nifti
 from .data import set_centre_draw
+from .functional import warp
 from .noise_stream import get_noise_plan
 from .noise_stream import set_noise_plan
 from .ops import get_resample_precision
@@ -100,5 +101,5 @@ __all__ = [
     "Gamma", "Ghosting", "GridSampler", "HistogramStandardization", "Image", "ImagesBatch", "ImagesLoader", "IntensityTransform", "KeepLargestComponent", "LabelMap", "LabelSampler", "LabelsToImage", "Lambda", "Mask", "Motion", "Noise", "Normalize", "OneHot", "OneOf",
     "PCA", "Pad", "PatchAggregator", "PatchLocation", "PatchSampler", "Points", "Queue", "RemapLabels", "RemoveLabels", "Reorient", "Resample", "RescaleIntensity", "Resize", "ScalarImage", "SequentialLabels", "SomeOf", "Spatial", "SpatialTransform", "Spike", "Standardize", "Subject", "Swap",
     "SubjectsBatch", "SubjectsLoader", "To", "ToReferenceSpace", "Transform", "Transpose", "UniformSampler", "WeightedSampler", "ZNormalization", "apply_inverse_transform", "calibrate_draw_policy", "get_centre_draw", "set_centre_draw", "get_draw_policy", "set_draw_policy", "get_noise_plan", "set_noise_plan", "get_inverse_transform", "get_noise_rng", "get_resample_precision", "get_stencil_precision", "set_noise_rng", "set_resample_precision", "set_stencil_precision",
-    "read_image", "write_nifti",
+    "read_image", "warp", "write_nifti",
 ]

@@ -19,5 +19,36 @@ class _AttachBackward(torch.autograd.Function):
         return ctx.backward_fn(grad.contiguous()), None, None
 
 
+class _AttachGeometryBackward(torch.autograd.Function):
+    """Give the results of one resampling call their dependence on its geometry: ``results`` were computed by a kernel from the
+    detached ``mapping`` / ``control_points`` (the leaves, or what leads to them); ``backward_fn(grads, want_mapping,
+    want_control_points)`` returns ``(dL/d mapping | None, dL/d control_points | None)`` as float32 device tensors, which are cast to
+    the dtype and moved to the device of the tensor they belong to.  The gradients of the results pass through unchanged (an image
+    that requires a gradient had its own backward attached before)."""
+
+    @staticmethod
+    def forward(ctx, backward_fn, mapping, control_points, *results):
+        ctx.backward_fn = backward_fn
+        ctx.like = [None if t is None else (t.shape, t.dtype, t.device) for t in (mapping, control_points)]
+        return tuple(result.view_as(result) for result in results)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        from ._lib import EngineError  # noqa: PLC0415
+
+        wants = ctx.needs_input_grad[1:3]
+        if torch.is_grad_enabled() and any(wants):
+            raise EngineError("resample3d: the gradient with respect to the mapping / control points cannot be differentiated again"
+                              " (no double backward through tio_resample3d_geometry_grad)")
+        geometry = [None, None]
+        if any(wants):
+            computed = ctx.backward_fn([None if grad is None else grad.contiguous() for grad in grads], wants[0], wants[1])
+            for slot, (value, like) in enumerate(zip(computed, ctx.like, strict=True)):
+                if wants[slot] and like is not None:
+                    shape, dtype, device = like
+                    geometry[slot] = torch.zeros(shape, dtype=dtype, device=device) if value is None else value.reshape(shape).to(device=device, dtype=dtype)
+        return (None, *geometry, *grads)
+
+
 def _wants_grad(tensor: Tensor | None) -> bool:
     return tensor is not None and torch.is_grad_enabled() and tensor.requires_grad

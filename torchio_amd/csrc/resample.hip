@@ -734,6 +734,12 @@ int check_geometry(const tio_resample_geom* geom, ResampleArgs& a) {
   return TIO_OK;
 }
 
+}  // namespace
+namespace tio {
+int resample_check_geometry(const tio_resample_geom* geom, ResampleArgs& a) { return check_geometry(geom, a); }
+}  // namespace tio
+namespace {
+
 NearestArgs make_nearest_args(const ResampleArgs& a) {
   NearestArgs nn{};
   nn.B = a.B; nn.I = a.I; nn.J = a.J; nn.K = a.K; nn.Io = a.Io; nn.Jo = a.Jo; nn.Ko = a.Ko; nn.affine_first = a.affine_first;

@@ -49,4 +49,8 @@ struct ResampleArgs {
   int plan_multi;    // plan_bricks_kernel: bricks whose box exceeds the tile get pass boxes over halves / quarters of their planes (the exact-coordinate lean kernel reads them)
   int fill_recheck;  // FAST kernels: voxels whose in-bounds weight is within a margin of 1/2 take the exact chain's decision (A/B: TIO_FAST_FILL_RECHECK=0)
 };
+
+// resample.hip: the checks of a tio_resample_geom and the part of ResampleArgs every launch of that geometry shares (an empty batch leaves
+// a.B == 0); for the entry points in other files that take the same geometry (resample_geometry_grad.hip)
+int resample_check_geometry(const tio_resample_geom* geom, ResampleArgs& a);
 }  // namespace tio

@@ -1,7 +1,7 @@
 // torch_ops.cpp — PyTorch-ROCm custom-op registration of the C ABI (BASELINE.json north_star:
 // "exposed through PyTorch-ROCm custom ops").
 //
-//   TORCH_LIBRARY(tio_hip, m): resample3d, separable_conv3d, bias_field_apply, add_noise, gamma_pow, channel_min,
+//   TORCH_LIBRARY(tio_hip, m): resample3d, resample3d_adjoint, resample3d_geometry_grad, separable_conv3d, bias_field_apply, add_noise, gamma_pow, channel_min,
 //                              bspline_prefilter
 //
 // Each op is a thin shim: it checks device / dtype / shapes (TORCH_CHECK -> Python RuntimeError), allocates the
@@ -17,6 +17,7 @@
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <torch/library.h>
 
+#include <tuple>
 #include <vector>
 
 #include "../../include/tio_hip.h"
@@ -183,6 +184,88 @@ at::Tensor resample3d_adjoint(const at::Tensor& grad, at::IntArrayRef in_shape, 
   return accumulator;
 }
 
+// resample3d_geometry_grad(Tensor[] images, Tensor[] grads, mapping, cp, spacings, int[3] out_shape, affine_first, Tensor?[] fill, passthrough)
+//   -> (Tensor d_mapping f32 like mapping, Tensor d_control_points f32 like cp, or an empty tensor without control points): the gradient of
+//   <resample3d(images), grads> with respect to the geometry (tio_resample3d_geometry_grad); images are float, resampled trilinearly.
+std::tuple<at::Tensor, at::Tensor> resample3d_geometry_grad(at::TensorList images, at::TensorList grads, const at::Tensor& mapping,
+                                                            const c10::optional<at::Tensor>& control_points, at::ArrayRef<double> in_spacing,
+                                                            at::ArrayRef<double> out_spacing, at::IntArrayRef out_shape, bool affine_first,
+                                                            const c10::List<c10::optional<at::Tensor>>& fill,
+                                                            const c10::optional<at::Tensor>& passthrough) {
+  const char* what = "resample3d_geometry_grad";
+  TORCH_CHECK(!images.empty() && images.size() <= TIO_MAX_IMAGES, what, ": 1..", TIO_MAX_IMAGES, " images per call");
+  TORCH_CHECK(grads.size() == images.size() && fill.size() == images.size(), what, ": one gradient and one fill entry per image");
+  TORCH_CHECK(in_spacing.size() == 3 && out_spacing.size() == 3 && out_shape.size() == 3, what, ": spacings and out_shape have 3 entries");
+  const at::Tensor& first = images[0];
+  check_volume(first, what);
+  const c10::hip::HIPGuardMasqueradingAsCUDA device_guard(first.device());
+  const at::Device device = first.device();
+  std::vector<at::Tensor> keep;
+  keep.reserve(4 * images.size() + 8);
+  tio_resample_geom geom{};
+  geom.batch = static_cast<int32_t>(first.size(0));
+  for (int d = 0; d < 3; d++) {
+    geom.in_shape[d] = static_cast<int32_t>(first.size(2 + d));
+    geom.out_shape[d] = static_cast<int32_t>(out_shape[d]);
+    geom.in_spacing[d] = static_cast<float>(in_spacing[d]);
+    geom.out_spacing[d] = static_cast<float>(out_spacing[d]);
+  }
+  geom.affine_first = affine_first ? 1 : 0;
+  TORCH_CHECK(mapping.device() == device && mapping.dim() == 3 && mapping.size(1) == 3 && mapping.size(2) == 4 &&
+                  (mapping.size(0) == 1 || mapping.size(0) == geom.batch),
+              what, ": mapping must be (B|1, 3, 4) on the data's device");
+  keep.push_back(mapping.to(at::kFloat).contiguous());
+  geom.mapping_dev = keep.back().data_ptr<float>();
+  geom.mapping_batched = mapping.size(0) > 1 ? 1 : 0;
+  at::Tensor d_mapping = at::empty(mapping.sizes(), mapping.options().dtype(at::kFloat));
+  at::Tensor d_control = at::empty({0}, mapping.options().dtype(at::kFloat));
+  if (control_points.has_value() && control_points->defined()) {
+    const at::Tensor& cp = *control_points;
+    TORCH_CHECK(cp.device() == device && cp.dim() == 5 && cp.size(4) == 3 && (cp.size(0) == 1 || cp.size(0) == geom.batch), what,
+                ": control points must be (B|1, ni, nj, nk, 3) on the data's device");
+    keep.push_back(cp.to(at::kFloat).contiguous());
+    geom.control_points_dev = keep.back().data_ptr<float>();
+    geom.cp_batched = cp.size(0) > 1 ? 1 : 0;
+    for (int d = 0; d < 3; d++) geom.cp_shape[d] = static_cast<int32_t>(cp.size(1 + d));
+    d_control = at::empty(cp.sizes(), cp.options().dtype(at::kFloat));
+  }
+  geom.passthrough_dev = opt_flags(passthrough, keep, device, geom.batch, what);
+  geom.precision = TIO_PRECISION_EXACT;
+
+  std::vector<tio_resample_image> descs(images.size());
+  for (size_t i = 0; i < images.size(); i++) {
+    check_volume(images[i], what);
+    check_volume(grads[i], what);
+    TORCH_CHECK(images[i].device() == device && grads[i].device() == device && images[i].size(0) == geom.batch, what,
+                ": images and gradients must share device and batch size");
+    TORCH_CHECK(at::isFloatingType(images[i].scalar_type()), what, ": floating-point images expected");
+    TORCH_CHECK(grads[i].size(0) == geom.batch && grads[i].size(1) == images[i].size(1) && grads[i].size(2) == out_shape[0] &&
+                    grads[i].size(3) == out_shape[1] && grads[i].size(4) == out_shape[2],
+                what, ": a gradient is shaped like its image's output, (B, C, *out_shape)");
+    keep.push_back(images[i].contiguous());
+    const at::Tensor& in = keep.back();
+    keep.push_back(grads[i].to(at::kFloat).contiguous());
+    const at::Tensor& g = keep.back();
+    tio_resample_image& d = descs[i];
+    d = tio_resample_image{};
+    d.in = in.data_ptr();
+    d.out = g.data_ptr();
+    d.channels = static_cast<int32_t>(in.size(1));
+    d.dtype = dtype_code(in.scalar_type());
+    d.interp = TIO_LINEAR;
+    const c10::optional<at::Tensor> f = fill.get(i);
+    if (f.has_value() && f->defined()) TORCH_CHECK(f->numel() == in.size(1), what, ": a fill tensor holds one value per channel");
+    d.fill_dev = opt_f32(f, keep, device, what);
+  }
+  const int64_t bytes = tio_resample3d_geometry_grad_workspace_bytes(&geom);
+  at::Tensor workspace = at::empty({(bytes + 7) / 8}, mapping.options().dtype(at::kDouble));
+  check_status(tio_resample3d_geometry_grad(&geom, static_cast<int32_t>(descs.size()), descs.data(), d_mapping.data_ptr<float>(),
+                                            geom.control_points_dev != nullptr ? d_control.data_ptr<float>() : nullptr, workspace.data_ptr(), bytes,
+                                            current_stream(first)),
+               "tio_resample3d_geometry_grad");
+  return std::make_tuple(d_mapping, d_control);
+}
+
 // separable_conv3d(Tensor x, Tensor taps(1|B,3,stride), int[3] radius, Tensor? skip(B)) -> Tensor
 at::Tensor separable_conv3d(const at::Tensor& x, const at::Tensor& taps, at::IntArrayRef radius, const c10::optional<at::Tensor>& skip) {
   check_volume(x, "separable_conv3d");
@@ -323,6 +406,8 @@ TORCH_LIBRARY(tio_hip, m) {
         "int[] out_shape, bool affine_first, Tensor?[] fill, Tensor? passthrough=None, int precision=0) -> Tensor[]");
   m.def("resample3d_adjoint(Tensor grad, int[] in_shape, Tensor mapping, Tensor? control_points, float[] in_spacing, float[] out_spacing, "
         "bool affine_first, Tensor? fill=None, Tensor? passthrough=None) -> Tensor");
+  m.def("resample3d_geometry_grad(Tensor[] images, Tensor[] grads, Tensor mapping, Tensor? control_points, float[] in_spacing, float[] out_spacing, "
+        "int[] out_shape, bool affine_first, Tensor?[] fill, Tensor? passthrough=None) -> (Tensor, Tensor)");
   m.def("separable_conv3d(Tensor x, Tensor taps, int[] radius, Tensor? skip=None) -> Tensor");
   m.def("bias_field_apply(Tensor x, Tensor coarse, bool divide=False, Tensor? skip=None) -> Tensor");
   m.def("add_noise(Tensor x, Tensor mean, Tensor std, bool rician=False, Tensor? base=None, Tensor? base2=None, int philox_seed=0, "
@@ -335,6 +420,7 @@ TORCH_LIBRARY(tio_hip, m) {
 TORCH_LIBRARY_IMPL(tio_hip, CUDA, m) {
   m.impl("resample3d", resample3d);
   m.impl("resample3d_adjoint", resample3d_adjoint);
+  m.impl("resample3d_geometry_grad", resample3d_geometry_grad);
   m.impl("separable_conv3d", separable_conv3d);
   m.impl("bias_field_apply", bias_field_apply);
   m.impl("add_noise", add_noise);

@@ -25,6 +25,7 @@ from . import _lib
 # The side streams (streams.py) and the reference's noise stream (noise_stream.py) are modules of their own; their public
 # names — and the error type and autograd helpers they share with the engine — are read through `ops` as well.
 from ._autograd import _AttachBackward
+from ._autograd import _AttachGeometryBackward
 from ._autograd import _wants_grad
 from ._lib import EngineError
 from .noise_stream import HostNormalStream
@@ -232,7 +233,9 @@ class Engine:
     detached data and attaches a backward: the adjoint scatter kernel for trilinear resampling
     (``TIO_LINEAR_ADJOINT``), the same multiply for the bias field, the flip for the flip, closed-form tensor algebra
     for gamma / noise, the transposed clamped stencil for the blur (``tio_separable_conv3d_adjoint``, round 6).
-    Parameters (mapping, control points, sigmas ...) are plain numbers in the reference too and get no gradient.
+    The geometry of a trilinear resampling is differentiable too: a ``mapping`` or ``control_points`` tensor that requires a
+    gradient receives one from ``tio_resample3d_geometry_grad`` (``resample3d``, ``resample3d_geometry_grad``).  The other
+    parameters (sigmas, gammas ...) are plain numbers in the reference too and get no gradient.
     """
 
     def __init__(self, functions: dict, device_type: str, name: str):
@@ -406,6 +409,13 @@ class Engine:
         batch = first.shape[0]
         in_shape = tuple(first.shape[2:])
         out_shape = tuple(int(s) for s in out_shape)
+        # geometry that takes part in autograd (a mapping or control points that require a gradient): the kernels see the detached
+        # float32 values on the images' device, the float trilinear outputs get `tio_resample3d_geometry_grad` as their backward
+        geometry_leaves = (mapping, control_points)
+        wants_geometry = _adjoint_of is None and (_wants_grad(mapping) or _wants_grad(control_points))
+        if wants_geometry:
+            mapping = h2d(mapping.detach().to(torch.float32), first.device)
+            control_points = None if control_points is None else h2d(control_points.detach().to(torch.float32), first.device)
         geom, keep_alive = self._resample_geom(
             batch, in_shape, out_shape, mapping, control_points, in_spacing, out_spacing, affine_first, cp_skip, passthrough,
             norm_shape, precision, large_boxes,
@@ -514,7 +524,110 @@ class Engine:
                     return accumulator.to(source.dtype)
 
                 outputs[n] = _AttachBackward.apply(source, outputs[n], backward)
+        if wants_geometry:
+            # every float trilinear output of the call joins ONE graph node, so that a backward pass launches once per MAX_IMAGES
+            # chunk whatever the number of outputs; the other images (label maps riding along) took part in the forward and carry
+            # no gradient
+            members = [n for n, t in enumerate(images) if t.dtype in FLOAT_DTYPES and codes[n] == _abi.LINEAR]
+            if members:
+                shared = dict(
+                    out_shape=out_shape, mapping=mapping, control_points=control_points, in_spacing=tuple(in_spacing),
+                    out_spacing=tuple(out_spacing), affine_first=affine_first, cp_skip=cp_skip, passthrough=passthrough, norm_shape=norm_shape,
+                )
+                data, member_fills = [images[n] for n in members], [fills[n] for n in members]
+
+                def geometry_backward(grads, want_mapping, want_control_points):
+                    present = [n for n, grad in enumerate(grads) if grad is not None]
+                    if not present:
+                        return None, None
+                    return self.resample3d_geometry_grad(
+                        [data[n] for n in present], [grads[n] for n in present], fills=[member_fills[n] for n in present],
+                        want_mapping=want_mapping, want_control_points=want_control_points, **shared)
+
+                attached = _AttachGeometryBackward.apply(geometry_backward, *geometry_leaves, *[outputs[n] for n in members])
+                for n, out in zip(members, attached, strict=True):
+                    outputs[n] = out
         return outputs
+
+    def resample3d_geometry_grad(
+        self,
+        images: Sequence[Tensor],
+        grads: Sequence[Tensor],
+        *,
+        out_shape: Sequence[int],
+        mapping: Tensor,
+        control_points: Tensor | None,
+        in_spacing: Sequence[float],
+        out_spacing: Sequence[float],
+        affine_first: bool,
+        fills: Sequence[Tensor | None],
+        cp_skip: Tensor | None = None,
+        passthrough: Tensor | None = None,
+        norm_shape: Sequence[int] | None = None,
+        want_mapping: bool = True,
+        want_control_points: bool = True,
+    ) -> tuple[Tensor | None, Tensor | None]:
+        """``d <resample3d(images), grads> / d(mapping, control_points)`` in one fused launch per ``MAX_IMAGES`` images
+        (``tio_resample3d_geometry_grad``: include/tio_hip.h has the definition).  *images* are the float tensors ``(B, C, I, J, K)``
+        that ``resample3d`` resampled trilinearly with this geometry and *fills*, *grads* the gradients ``(B, C, *out_shape)`` of
+        their outputs.  Returns float32 tensors in the shapes of *mapping* ``(1|B, 3, 4)`` and *control_points*, ``None`` for the
+        one that is not wanted (or, for the control points, not there).  Nothing here takes part in autograd."""
+        if not images or not (len(images) == len(grads) == len(fills)):
+            raise ValueError("images, grads and fills must be non-empty and of the same length")
+        want_control_points = want_control_points and control_points is not None
+        if not (want_mapping or want_control_points):
+            return None, None
+        first = images[0]
+        if first.ndim != 5:
+            raise ValueError(f"expected (B, C, I, J, K) tensors, got {tuple(first.shape)}")
+        batch, in_shape, out_shape = first.shape[0], tuple(first.shape[2:]), tuple(int(s) for s in out_shape)
+        with torch.no_grad():
+            geom, keep_alive = self._resample_geom(
+                batch, in_shape, out_shape, mapping.detach(), None if control_points is None else control_points.detach(), in_spacing,
+                out_spacing, affine_first, cp_skip, passthrough, norm_shape, "exact",
+            )
+            mapping, control_points = keep_alive[:2]
+            d_mapping = torch.empty_like(mapping) if want_mapping else None
+            d_control = torch.empty_like(control_points) if want_control_points else None
+            nbytes = int(self._fn["resample3d_geometry_grad_workspace_bytes"](C.byref(geom)))
+            workspace = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=first.device)
+            total_mapping = total_control = None
+            for start in range(0, len(images), _abi.MAX_IMAGES):
+                chunk = range(start, min(start + _abi.MAX_IMAGES, len(images)))
+                descs = (_abi.ResampleImage * len(chunk))()
+                for slot, n in enumerate(chunk):
+                    data, grad, fill = images[n].detach(), grads[n].detach(), fills[n]
+                    if data.ndim != 5 or data.shape[0] != batch or tuple(data.shape[2:]) != in_shape:
+                        raise ValueError("all images must share the batch size and spatial shape")
+                    if data.dtype not in FLOAT_DTYPES:
+                        raise EngineError("resample3d_geometry_grad: only floating-point images resampled trilinearly carry a geometry gradient")
+                    if tuple(grad.shape) != (batch, data.shape[1], *out_shape):
+                        raise ValueError("gradient shape does not match the forward output")
+                    data, grad = data.contiguous(), grad.to(torch.float32).contiguous()
+                    if fill is not None:
+                        if fill.dtype != torch.float32 or fill.device != data.device or not fill.is_contiguous():
+                            fill = h2d(fill.to(torch.float32), data.device).contiguous()
+                        if fill.numel() != data.shape[1]:
+                            raise ValueError("fill must have one value per channel")
+                    self._check("resample3d_geometry_grad", data, grad, fill)
+                    descs[slot].in_ = data.data_ptr()
+                    descs[slot].out = grad.data_ptr()
+                    descs[slot].channels = data.shape[1]
+                    descs[slot].dtype = dtype_code(data.dtype)
+                    descs[slot].interp = _abi.LINEAR
+                    descs[slot].fill_dev = None if fill is None else fill.data_ptr()
+                    keep_alive += [data, grad, fill]
+                if start > 0:  # a further chunk: fresh outputs, summed below (the launch overwrites its outputs)
+                    total_mapping, total_control = d_mapping, d_control
+                    d_mapping = torch.empty_like(mapping) if want_mapping else None
+                    d_control = torch.empty_like(control_points) if want_control_points else None
+                self._call("resample3d_geometry_grad", first, C.byref(geom), len(chunk), descs, _ptr(d_mapping), _ptr(d_control), _ptr(workspace),
+                           nbytes, self._stream(first))
+                if start > 0:
+                    d_mapping = None if d_mapping is None else total_mapping + d_mapping
+                    d_control = None if d_control is None else total_control + d_control
+            del keep_alive
+        return d_mapping, d_control
 
     def bspline_prefilter(self, data: Tensor, order: int) -> Tensor:
         """B-spline coefficients (float32) of a ``(B, C, I, J, K)`` tensor for ``resample3d``'s ``"quadratic"`` (order 2) /

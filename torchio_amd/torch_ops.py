@@ -16,7 +16,7 @@ Round 3: the ops are full citizens of the dispatcher — **fake (meta) kernels**
 (``torch.library.register_fake``: FakeTensor / ``torch.compile`` tracing, ``torch.library.opcheck``), and the **backward
 passes are registered with autograd** (``torch.library.register_autograd``) like the reference's compositions of torch
 ops are differentiable (reference tests/test_noise.py:75-80): the trilinear resampling through the adjoint launch
-(``resample3d_adjoint``), the bias field through the same multiply, noise through the identity (Rician: ``(x + n1) / y``),
+(``resample3d_adjoint``) for the images and the fused reduction (``resample3d_geometry_grad``) for the mapping and the control points, the bias field through the same multiply, noise through the identity (Rician: ``(x + n1) / y``),
 gamma through ``g |x|^(g-1)``, the stencil through its transposed kernel (``tio_separable_conv3d_adjoint``, round 6).
 """
 from __future__ import annotations
@@ -65,6 +65,12 @@ def _register_dispatcher_extras() -> None:
     def _(grad, in_shape, mapping, control_points, in_spacing, out_spacing, affine_first, fill=None, passthrough=None):
         return grad.new_empty((grad.shape[0], grad.shape[1], *in_shape), dtype=torch.float32)
 
+    @lib.register_fake("tio_hip::resample3d_geometry_grad")
+    def _(images, grads, mapping, control_points, in_spacing, out_spacing, out_shape, affine_first, fill, passthrough=None):
+        d_mapping = mapping.new_empty(mapping.shape, dtype=torch.float32)
+        d_control = mapping.new_empty((0,), dtype=torch.float32) if control_points is None else control_points.new_empty(control_points.shape, dtype=torch.float32)
+        return d_mapping, d_control
+
     for name in ("separable_conv3d", "bias_field_apply", "add_noise", "gamma_pow"):
         lib.register_fake(f"tio_hip::{name}")(lambda x, *args, **kwargs: torch.empty_like(x))
 
@@ -86,6 +92,10 @@ def _register_dispatcher_extras() -> None:
         ctx.in_shapes = [tuple(int(v) for v in image.shape[2:]) for image in images]
         ctx.dtypes = [image.dtype for image in images]
         ctx.needs = [image.requires_grad for image in images]
+        ctx.out_shape = [int(v) for v in out_shape]
+        # the geometry's gradient needs the images: saved only when somebody will ask for it
+        ctx.geometry_needs = (mapping.requires_grad, control_points is not None and control_points.requires_grad)
+        ctx.images = [image.detach() for image in images] if any(ctx.geometry_needs) else None
 
     def resample_backward(ctx, grads):
         mapping, control_points, in_spacing, out_spacing, affine_first, passthrough = ctx.geometry
@@ -112,6 +122,18 @@ def _register_dispatcher_extras() -> None:
         except (AttributeError, TypeError, ValueError):
             structure = [None] * ctx.n_inputs
         structure[0] = image_grads
+        if any(ctx.geometry_needs):  # one fused launch for the float trilinear images that received a gradient; the others add nothing
+            members = [n for n, grad in enumerate(grads) if grad is not None and ctx.modes[n] == _LINEAR and ctx.dtypes[n].is_floating_point]
+            d_mapping = d_control = None
+            if members:
+                d_mapping, d_control = torch.ops.tio_hip.resample3d_geometry_grad(
+                    [ctx.images[n] for n in members], [grads[n] for n in members], mapping.detach(),
+                    None if control_points is None else control_points.detach(), in_spacing, out_spacing, ctx.out_shape, affine_first,
+                    [ctx.fills[n] for n in members], passthrough)
+            if ctx.geometry_needs[0]:
+                structure[2] = torch.zeros_like(mapping) if d_mapping is None else d_mapping.to(mapping.dtype)
+            if ctx.geometry_needs[1]:
+                structure[3] = torch.zeros_like(control_points) if d_control is None else d_control.to(control_points.dtype)
         return tuple(structure)
 
     lib.register_autograd("tio_hip::resample3d", resample_backward, setup_context=resample_setup)
