@@ -462,6 +462,58 @@ int tio_gamma_pow(const void* x, void* y, int32_t dtype, int32_t batch,
                   int64_t n_per_element, float gamma, const float* gamma_dev,
                   int32_t params_batched, void* stream);
 
+/*
+ * The gradients of the four intensity operations above with respect to their PARAMETERS (additive to ABI 18, HIP only): what
+ * autograd derives through the reference's compositions of torch operations (bias_field.py:237-244, blur.py:157-252,
+ * x + (mean + std z), sign(x) |x|^gamma) at the cost of a full-size field and a full-size gradient of it per parameter.  Each is
+ * one reduction of the volume into a handful of numbers: one read of x and of the incoming gradient, no per-voxel intermediate.
+ * Common to the four:
+ *   gy         float32, shaped like the forward's output: dL/d(output); x has `element_type`, a tio_dtype code: one of the four
+ *              float types (any other code: TIO_ERR_UNSUPPORTED_DTYPE);
+ *   terms      formed in float32 from the forward's own float32 values (y before its store rounds it, the same lerp weights, the
+ *              same expf / powf; float64 data: the forward's float64 expressions for gamma and noise, narrowed once for bias and
+ *              taps), summed in float64 from the lane up, float64 hardware atomics across blocks, ONE rounding to float32:
+ *              two runs differ at most in the last float32 rounding of an output;
+ *   workspace  *_workspace_bytes(...) bytes on the device, 8-byte aligned; its contents on entry do not matter;
+ *   outputs    float32, fully overwritten; flagged rows (skip_dev set, keep_dev == 0) add exactly zero; parameters shared across
+ *              the batch receive the sum over the batch;
+ *   errors     bad arguments return TIO_ERR_INVALID_ARGUMENT with nothing launched.
+ *
+ * tio_bias_field_grad: arguments as tio_bias_field_apply.  d_coarse (B, C, si, sj, sk):
+ *   d_coarse[b,c,n] = s * sum_v gy[b,c,v] * y[b,c,v] * W(n; v),  s = +1 (multiply) / -1 (divide), W the product of the three
+ *   align-corners lerp weights of the forward.
+ * tio_gamma_grad: arguments as tio_gamma_pow (and: a non-NULL gamma_dev without params_batched holds the one shared exponent, so a
+ *   device scalar needs no host round trip; likewise mean_dev / std_dev below).  d_gamma (B floats when params_batched, else 1):
+ *   d_gamma[b] = sum_{v: x != 0} gy * y * log|x|   (x == 0 adds nothing: ATen's rule for pow with respect to the exponent).
+ * tio_noise_grad: arguments as tio_add_noise.  d_mean, d_std (B floats when params_batched, else 1); either may be NULL, not both.
+ *   additive: d_mean[b] = sum gy, d_std[b] = sum gy * z (x may be NULL);
+ *   rician, a = x + n1, n_i = mean + std z_i:  d_mean = sum gy (a + n2) / y,  d_std = sum gy (a z1 + n2 z2) / y;  y == 0 adds nothing;
+ *   base1_dev == NULL: z is regenerated in the kernel, bit for bit the draws of tio_philox_normal (stream ids 0 and 1).
+ * tio_separable_conv3d_taps_grad: arguments as tio_separable_conv3d_adjoint, plus x with its element type.  d_taps in the layout of
+ *   taps_dev ((B | 1, 3, tap_stride); zero beyond 2 * radius[a] + 1 and on axes with radius 0).  With y = A_K A_J A_I x:
+ *   dW_I[t] = sum_v (A_J^T A_K^T gy)[v] x[clamp(v + (t - r) e_I)],  dW_J[t] = sum_v (A_K^T gy)[v] (A_I x)[clamp(v + (t - r) e_J)],
+ *   dW_K[t] = sum_v gy[v] (A_J A_I x)[clamp(v + (t - r) e_K)];  the intermediates are single-axis launches of
+ *   tio_separable_conv3d / tio_separable_conv3d_adjoint into `scratch` (2 x the volume, in floats).  Radii up to 16.
+ */
+int64_t tio_bias_field_grad_workspace_bytes(int32_t batch, int32_t channels, const int32_t coarse_shape[3]);
+int tio_bias_field_grad(const void* x, const float* gy, int32_t element_type, int32_t batch, int32_t channels, const int32_t shape[3],
+                        const float* coarse_dev, const int32_t coarse_shape[3], int32_t divide, const uint8_t* skip_dev,
+                        float* d_coarse, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t tio_gamma_grad_workspace_bytes(int32_t batch, int32_t params_batched);
+int tio_gamma_grad(const void* x, const float* gy, int32_t element_type, int32_t batch, int64_t n_per_element, float gamma,
+                   const float* gamma_dev, int32_t params_batched, float* d_gamma, void* workspace, int64_t workspace_bytes,
+                   void* stream);
+int64_t tio_noise_grad_workspace_bytes(int32_t batch, int32_t params_batched);
+int tio_noise_grad(const void* x, const float* gy, int32_t element_type, int32_t batch, int64_t n_per_element, float mean, float std,
+                   const float* mean_dev, const float* std_dev, int32_t params_batched, int32_t rician, const float* base1_dev,
+                   const float* base2_dev, uint64_t philox_seed, const uint8_t* keep_dev, float* d_mean, float* d_std,
+                   void* workspace, int64_t workspace_bytes, void* stream);
+int64_t tio_separable_conv3d_taps_grad_workspace_bytes(int32_t batch, int32_t taps_batched);
+int tio_separable_conv3d_taps_grad(const void* x, int32_t element_type, const float* gy, float* scratch, int32_t batch, int32_t channels,
+                                   const int32_t shape[3], const float* taps_dev, int32_t taps_batched, int32_t tap_stride,
+                                   const int32_t radius[3], const uint8_t* skip_dev, float* d_taps, void* workspace,
+                                   int64_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------ */
 /* F.interpolate users: Resize, Anisotropy                */
 /* ------------------------------------------------------------------------ */

@@ -50,5 +50,36 @@ class _AttachGeometryBackward(torch.autograd.Function):
         return (None, *geometry, *grads)
 
 
+class _AttachParameterBackward(torch.autograd.Function):
+    """Give the result of an intensity op its dependence on the op's parameters (the coarse bias grid, the blur taps, the noise
+    mean / deviation, the gamma exponent): ``result`` was computed by a kernel from the detached ``parameters`` (the leaves, or
+    what leads to them; ``None`` for one that is a plain number).  ``backward_fn(grad, wants)`` returns one float32 device tensor
+    (or ``None``) per parameter, which is cast to the dtype and moved to the device of the tensor it belongs to.  The gradient of
+    the result passes through unchanged (data that requires a gradient had its own backward attached before)."""
+
+    @staticmethod
+    def forward(ctx, what, backward_fn, result, *parameters):
+        ctx.what, ctx.backward_fn = what, backward_fn
+        ctx.like = [None if t is None else (t.shape, t.dtype, t.device) for t in parameters]
+        return result.view_as(result)
+
+    @staticmethod
+    def backward(ctx, grad):
+        from ._lib import EngineError  # noqa: PLC0415
+
+        wants = ctx.needs_input_grad[3:]
+        if torch.is_grad_enabled() and any(wants):
+            raise EngineError(f"{ctx.what}: the gradient with respect to the parameters cannot be differentiated again"
+                              " (no double backward through the parameter-gradient kernels)")
+        out = [None] * len(wants)
+        if any(wants):
+            computed = ctx.backward_fn(grad.contiguous(), wants)
+            for slot, (value, like) in enumerate(zip(computed, ctx.like, strict=True)):
+                if wants[slot] and like is not None:
+                    shape, dtype, device = like
+                    out[slot] = torch.zeros(shape, dtype=dtype, device=device) if value is None else value.reshape(shape).to(device=device, dtype=dtype)
+        return (None, None, grad, *out)
+
+
 def _wants_grad(tensor: Tensor | None) -> bool:
     return tensor is not None and torch.is_grad_enabled() and tensor.requires_grad

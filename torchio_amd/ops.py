@@ -26,6 +26,7 @@ from . import _lib
 # names — and the error type and autograd helpers they share with the engine — are read through `ops` as well.
 from ._autograd import _AttachBackward
 from ._autograd import _AttachGeometryBackward
+from ._autograd import _AttachParameterBackward
 from ._autograd import _wants_grad
 from ._lib import EngineError
 from .noise_stream import HostNormalStream
@@ -234,8 +235,10 @@ class Engine:
     (``TIO_LINEAR_ADJOINT``), the same multiply for the bias field, the flip for the flip, closed-form tensor algebra
     for gamma / noise, the transposed clamped stencil for the blur (``tio_separable_conv3d_adjoint``, round 6).
     The geometry of a trilinear resampling is differentiable too: a ``mapping`` or ``control_points`` tensor that requires a
-    gradient receives one from ``tio_resample3d_geometry_grad`` (``resample3d``, ``resample3d_geometry_grad``).  The other
-    parameters (sigmas, gammas ...) are plain numbers in the reference too and get no gradient.
+    gradient receives one from ``tio_resample3d_geometry_grad`` (``resample3d``, ``resample3d_geometry_grad``).  So are the
+    parameters of the intensity ops: a coarse bias grid, blur taps, a noise mean / deviation or a gamma exponent that requires a
+    gradient receives one from the fused reductions of ``intensity_param_grad.hip`` (``bias_field_grad``, ``separable_conv3d_taps_grad``,
+    ``noise_grad``, ``gamma_grad``); plain numbers get none.
     """
 
     def __init__(self, functions: dict, device_type: str, name: str):
@@ -286,6 +289,17 @@ class Engine:
         if flags.dtype not in (torch.uint8, torch.bool) or flags.numel() != batch:
             raise ValueError(f"{what} must hold {batch} uint8/bool flags")
         return flags.to(torch.uint8).contiguous()
+
+    def _parameter_kernel(self, name: str, what: str) -> None:
+        """A parameter that requires a gradient needs ``tio_<name>``: only the HIP library has it (no quiet ``None``)."""
+        if name not in self._fn:
+            raise NotImplementedError(
+                f"{what} requires a gradient, but the {self.name} engine has no tio_{name}: the parameter gradients of the intensity"
+                " ops exist on the HIP engine only - detach the parameter, or run on the GPU")
+
+    def _workspace(self, name: str, ref: Tensor, *args) -> tuple[Tensor, int]:
+        nbytes = int(self._fn[name](*args))
+        return torch.empty(max(1, (nbytes + 7) // 8), dtype=torch.float64, device=ref.device), nbytes
 
     # -- spatial ------------------------------------------------------------
     def _resample_geom(
@@ -670,6 +684,12 @@ class Engine:
             raise ValueError("expected a (B, C, I, J, K) tensor")
         if data.dtype not in FLOAT_DTYPES:
             raise TypeError(f"separable_conv3d needs a floating dtype, got {data.dtype}")
+        if _wants_grad(taps):  # the kernel sees the detached float32 taps on the data's device; the result gets the tap correlation as its backward
+            self._parameter_kernel("separable_conv3d_taps_grad", "separable_conv3d: taps")
+            values, source = h2d(taps.detach().to(torch.float32), data.device), data.detach()
+            result = self.separable_conv3d(data, values, radius, skip=skip)
+            return _AttachParameterBackward.apply(
+                "separable_conv3d", lambda grad, wants: [self.separable_conv3d_taps_grad(source, grad, values, radius, skip=skip)], result, taps)
         if _wants_grad(data):
             detached = data.detach()
             result = self.separable_conv3d(detached, taps, radius, skip=skip)
@@ -789,6 +809,12 @@ class Engine:
             raise ValueError("data and coarse must be 5-D with the same (B, C)")
         if data.dtype not in FLOAT_DTYPES:
             raise TypeError(f"bias_field_apply needs a floating dtype, got {data.dtype}")
+        if _wants_grad(coarse):
+            self._parameter_kernel("bias_field_grad", "bias_field_apply: coarse")
+            values, source = h2d(coarse.detach().to(torch.float32), data.device), data.detach()
+            result = self.bias_field_apply(data, values, divide=divide, skip=skip)
+            return _AttachParameterBackward.apply(
+                "bias_field_apply", lambda grad, wants: [self.bias_field_grad(source, grad, values, divide=divide, skip=skip)], result, coarse)
         if _wants_grad(data):  # y = x * f (or x / f): the gradient is the same multiply applied to the incoming gradient
             result = self.bias_field_apply(data.detach(), coarse, divide=divide, skip=skip)
             return _AttachBackward.apply(data, result, lambda grad: self.bias_field_apply(grad.to(data.dtype), coarse, divide=divide, skip=skip))
@@ -819,6 +845,18 @@ class Engine:
         """``data + (mean + std * z)``; ``z`` from *base1*/*base2* or in-kernel Philox when ``None``."""
         if data.dtype not in FLOAT_DTYPES:
             raise TypeError(f"add_noise needs a floating dtype, got {data.dtype}")
+        leaves = [p if isinstance(p, Tensor) and _wants_grad(p) else None for p in (mean, std)]
+        if any(leaf is not None for leaf in leaves):
+            self._parameter_kernel("noise_grad", "add_noise: mean / std")
+            mean_v, std_v = (h2d(p.detach().to(torch.float32), data.device) if isinstance(p, Tensor) else p for p in (mean, std))
+            source = data.detach()
+            result = self.add_noise(data, mean_v, std_v, rician=rician, base1=base1, base2=base2, philox_seed=philox_seed, keep=keep)
+
+            def parameter_backward(grad, wants):
+                return list(self.noise_grad(source, grad, mean_v, std_v, rician=rician, base1=base1, base2=base2, philox_seed=philox_seed,
+                                            keep=keep, want_mean=wants[0], want_std=wants[1]))
+
+            return _AttachParameterBackward.apply("add_noise", parameter_backward, result, *leaves)
         if _wants_grad(data):
             detached = data.detach()
             result = self.add_noise(detached, mean, std, rician=rician, base1=base1, base2=base2, philox_seed=philox_seed, keep=keep)
@@ -877,6 +915,11 @@ class Engine:
         """``sign(data) * |data| ** gamma`` with a scalar or per-element ``(B,)`` exponent."""
         if data.dtype not in FLOAT_DTYPES:
             raise TypeError(f"gamma_pow needs a floating dtype, got {data.dtype}")
+        if isinstance(gamma, Tensor) and _wants_grad(gamma):
+            self._parameter_kernel("gamma_grad", "gamma_pow: gamma")
+            values, source = h2d(gamma.detach().to(torch.float32), data.device), data.detach()
+            result = self.gamma_pow(data, values)
+            return _AttachParameterBackward.apply("gamma_pow", lambda grad, wants: [self.gamma_grad(source, grad, values)], result, gamma)
         if _wants_grad(data):  # y = sign(x) |x|^g: dy/dx = g |x|^(g - 1)
             detached = data.detach()
             result = self.gamma_pow(detached, gamma)
@@ -898,6 +941,146 @@ class Engine:
             data[0].numel() if batch else 0, 0.0 if gamma_t is not None else float(gamma), _ptr(gamma_t),
             int(gamma_t is not None), self._stream(data),
         )
+        return out
+
+    # -- gradients with respect to the parameters of the four ops above (intensity_param_grad.hip; nothing here takes part in autograd)
+    def _grad_pair(self, what: str, data: Tensor, grad: Tensor) -> tuple[Tensor, Tensor]:
+        if data.dtype not in FLOAT_DTYPES:
+            raise TypeError(f"{what} needs a floating dtype, got {data.dtype}")
+        if tuple(grad.shape) != tuple(data.shape):
+            raise ValueError(f"{what}: the gradient {tuple(grad.shape)} is not shaped like the data {tuple(data.shape)}")
+        return data.detach().contiguous(), grad.detach().to(torch.float32).contiguous()
+
+    def _shared_or_batched(self, value: float | Tensor, batch: int, device, what: str) -> Tensor | float:
+        """A parameter as the kernels take it: a number, or a float32 device tensor of 1 or *batch* values."""
+        if not isinstance(value, Tensor):
+            return float(value)
+        if value.numel() not in (1, batch):
+            raise ValueError(f"{what} must hold 1 or {batch} values, got {tuple(value.shape)}")
+        return h2d(value.detach().to(torch.float32), device).reshape(-1).contiguous()
+
+    def bias_field_grad(self, data: Tensor, grad: Tensor, coarse: Tensor, *, divide: bool = False, skip: Tensor | None = None) -> Tensor:
+        """``d <bias_field_apply(data, coarse), grad> / d coarse`` as a float32 tensor shaped like *coarse* (``tio_bias_field_grad``):
+        ``s * sum_v grad * y * W(node; v)`` with the forward's own field and lerp weights, one read of *data* and *grad*."""
+        if data.ndim != 5 or coarse.ndim != 5 or coarse.shape[:2] != data.shape[:2]:
+            raise ValueError("data and coarse must be 5-D with the same (B, C)")
+        with torch.no_grad():
+            data, grad = self._grad_pair("bias_field_grad", data, grad)
+            coarse = h2d(coarse.detach().to(torch.float32), data.device).contiguous()
+            skip = self._flags(skip, data.shape[0], "skip")
+            if skip is not None and skip.device != data.device:
+                skip = skip.to(data.device)
+            self._check("bias_field_grad", data, grad, coarse, skip)
+            out = torch.empty_like(coarse)
+            workspace, nbytes = self._workspace("bias_field_grad_workspace_bytes", data, data.shape[0], data.shape[1], _i32x3(coarse.shape[2:]))
+            self._call(
+                "bias_field_grad", data, _ptr(data), _ptr(grad), dtype_code(data.dtype), data.shape[0], data.shape[1], _i32x3(data.shape[2:]),
+                _ptr(coarse), _i32x3(coarse.shape[2:]), int(bool(divide)), _ptr(skip), _ptr(out), _ptr(workspace), nbytes, self._stream(data),
+            )
+        return out
+
+    def gamma_grad(self, data: Tensor, grad: Tensor, gamma: float | Tensor) -> Tensor:
+        """``d <gamma_pow(data, gamma), grad> / d gamma`` (``tio_gamma_grad``): ``sum grad * y * log|x|`` over ``x != 0``, float32,
+        one value per element for a ``(B,)`` exponent (``B > 1``), else one value."""
+        with torch.no_grad():
+            data, grad = self._grad_pair("gamma_grad", data, grad)
+            batch = data.shape[0]
+            gamma = self._shared_or_batched(gamma, batch, data.device, "gamma")
+            gamma_t = gamma if isinstance(gamma, Tensor) else None
+            batched = gamma_t is not None and gamma_t.numel() == batch and batch > 1
+            self._check("gamma_grad", data, grad, gamma_t)
+            out = torch.empty(batch if batched else 1, dtype=torch.float32, device=data.device)
+            workspace, nbytes = self._workspace("gamma_grad_workspace_bytes", data, batch, int(batched))
+            self._call(
+                "gamma_grad", data, _ptr(data), _ptr(grad), dtype_code(data.dtype), batch, data[0].numel() if batch else 0,
+                0.0 if gamma_t is not None else gamma, _ptr(gamma_t), int(batched), _ptr(out), _ptr(workspace), nbytes, self._stream(data),
+            )
+        return out
+
+    def noise_grad(
+        self,
+        data: Tensor,
+        grad: Tensor,
+        mean: float | Tensor,
+        std: float | Tensor,
+        *,
+        rician: bool = False,
+        base1: Tensor | None = None,
+        base2: Tensor | None = None,
+        philox_seed: int = 0,
+        keep: Tensor | None = None,
+        want_mean: bool = True,
+        want_std: bool = True,
+    ) -> tuple[Tensor | None, Tensor | None]:
+        """``d <add_noise(data, mean, std, ...), grad> / d (mean, std)`` (``tio_noise_grad``), float32, ``None`` for the one that
+        is not wanted.  With *base1* ``None`` the draws are regenerated from *philox_seed* in the kernel.  Each result has as many
+        values as its parameter (a number counts as one); where one parameter holds ``B`` values and the other one, the single
+        one's ``B`` per-element sums are added in float64."""
+        if not (want_mean or want_std):
+            return None, None
+        with torch.no_grad():
+            data, grad = self._grad_pair("noise_grad", data, grad)
+            batch = data.shape[0]
+            mean = self._shared_or_batched(mean, batch, data.device, "mean")
+            std = self._shared_or_batched(std, batch, data.device, "std")
+            sizes = [p.numel() if isinstance(p, Tensor) else 1 for p in (mean, std)]
+            batched = batch > 1 and max(sizes) == batch
+            mean_t = std_t = None
+            if isinstance(mean, Tensor) or isinstance(std, Tensor):  # device values: B of each when either holds B, else the shared ones
+                count = batch if batched else 1
+                mean_t = torch.as_tensor(mean, dtype=torch.float32, device=data.device).expand(count).contiguous()
+                std_t = torch.as_tensor(std, dtype=torch.float32, device=data.device).expand(count).contiguous()
+            for base in (base1, base2):
+                if base is not None and (base.shape != data.shape or base.dtype != torch.float32):
+                    raise ValueError("base noise must be float32 and shaped like data")
+            base1 = None if base1 is None else base1.detach().contiguous()
+            base2 = None if base2 is None else base2.detach().contiguous()
+            keep = self._flags(keep, batch, "keep")
+            if keep is not None and keep.device != data.device:
+                keep = keep.to(data.device)
+            self._check("noise_grad", data, grad, mean_t, std_t, base1, base2, keep)
+            groups = batch if batched else 1
+            d_mean = torch.empty(groups, dtype=torch.float32, device=data.device) if want_mean else None
+            d_std = torch.empty(groups, dtype=torch.float32, device=data.device) if want_std else None
+            workspace, nbytes = self._workspace("noise_grad_workspace_bytes", data, batch, int(batched))
+            self._call(
+                "noise_grad", data, _ptr(data), _ptr(grad), dtype_code(data.dtype), batch, data[0].numel() if batch else 0,
+                0.0 if mean_t is not None else mean, 0.0 if std_t is not None else std, _ptr(mean_t), _ptr(std_t), int(batched),
+                int(bool(rician)), _ptr(base1), _ptr(base2), int(philox_seed) & (2**64 - 1), _ptr(keep), _ptr(d_mean), _ptr(d_std),
+                _ptr(workspace), nbytes, self._stream(data),
+            )
+            if batched:  # a single value next to B of the other: its per-element sums, added in float64
+                if d_mean is not None and sizes[0] == 1:
+                    d_mean = d_mean.double().sum().float().reshape(1)
+                if d_std is not None and sizes[1] == 1:
+                    d_std = d_std.double().sum().float().reshape(1)
+        return d_mean, d_std
+
+    def separable_conv3d_taps_grad(self, data: Tensor, grad: Tensor, taps: Tensor, radius: Sequence[int], skip: Tensor | None = None) -> Tensor:
+        """``d <separable_conv3d(data, taps, radius), grad> / d taps`` as a float32 tensor shaped like *taps*
+        (``tio_separable_conv3d_taps_grad``): per active axis one clamped tap correlation of the gradient carried back through the
+        later axes with the data carried forward through the earlier ones; zero beyond ``2 * radius + 1``."""
+        if data.ndim != 5:
+            raise ValueError("expected a (B, C, I, J, K) tensor")
+        with torch.no_grad():
+            data, grad = self._grad_pair("separable_conv3d_taps_grad", data, grad)
+            batch, channels = data.shape[:2]
+            taps = h2d(taps.detach().to(torch.float32), data.device).contiguous()
+            if taps.ndim != 3 or taps.shape[1] != 3 or taps.shape[0] not in (1, batch):
+                raise ValueError(f"taps must be (1|B, 3, stride), got {tuple(taps.shape)}")
+            skip = self._flags(skip, batch, "skip")
+            if skip is not None and skip.device != data.device:
+                skip = skip.to(data.device)
+            self._check("separable_conv3d_taps_grad", data, grad, taps, skip)
+            batched = int(taps.shape[0] == batch and batch > 1)
+            out = torch.empty_like(taps)
+            scratch = torch.empty((2, *data.shape), dtype=torch.float32, device=data.device)
+            workspace, nbytes = self._workspace("separable_conv3d_taps_grad_workspace_bytes", data, batch, batched)
+            self._call(
+                "separable_conv3d_taps_grad", data, _ptr(data), dtype_code(data.dtype), _ptr(grad), _ptr(scratch), batch, channels,
+                _i32x3(data.shape[2:]), _ptr(taps), batched, taps.shape[2], _i32x3(radius), _ptr(skip), _ptr(out), _ptr(workspace), nbytes,
+                self._stream(data),
+            )
         return out
 
 

@@ -18,6 +18,12 @@ passes are registered with autograd** (``torch.library.register_autograd``) like
 ops are differentiable (reference tests/test_noise.py:75-80): the trilinear resampling through the adjoint launch
 (``resample3d_adjoint``) for the images and the fused reduction (``resample3d_geometry_grad``) for the mapping and the control points, the bias field through the same multiply, noise through the identity (Rician: ``(x + n1) / y``),
 gamma through ``g |x|^(g-1)``, the stencil through its transposed kernel (``tio_separable_conv3d_adjoint``, round 6).
+
+The PARAMETERS of the four intensity ops are differentiable too: ``bias_field_grad``, ``gamma_grad``, ``noise_grad``
+and ``separable_conv3d_taps_grad`` are ops of their own (defined here on the ``ctypes`` engine, with fake kernels), and the
+backward passes of ``bias_field_apply``, ``gamma_pow``, ``add_noise`` and ``separable_conv3d`` fill the coarse / gamma / mean /
+std / taps slots with them.  ``philox_normal_like`` regenerates the in-kernel draws, so Rician noise with Philox draws
+backpropagates to its data as well.
 """
 from __future__ import annotations
 
@@ -49,9 +55,67 @@ def load() -> None:
 _LINEAR, _NEAREST = 1, 0
 
 
+def _define_parameter_gradient_ops() -> None:
+    """``tio_hip::*_grad`` and ``philox_normal_like``: the parameter-gradient launches as dispatcher ops (so that a backward pass
+    that uses them can be traced), on the ``ctypes`` engine over ``libtio_hip.so``."""
+    from . import ops  # noqa: PLC0415
+
+    define = torch.library.custom_op
+
+    @define("tio_hip::bias_field_grad", mutates_args=(), device_types="cuda", schema="(Tensor x, Tensor grad, Tensor coarse, bool divide=False, Tensor? skip=None) -> Tensor")
+    def bias_field_grad(x, grad, coarse, divide=False, skip=None):
+        return ops.hip_engine().bias_field_grad(x, grad, coarse, divide=divide, skip=skip)
+
+    @bias_field_grad.register_fake
+    def _(x, grad, coarse, divide=False, skip=None):
+        return coarse.new_empty(coarse.shape, dtype=torch.float32, device=x.device)
+
+    @define("tio_hip::gamma_grad", mutates_args=(), device_types="cuda", schema="(Tensor x, Tensor grad, Tensor gamma) -> Tensor")
+    def gamma_grad(x, grad, gamma):
+        return ops.hip_engine().gamma_grad(x, grad, gamma)
+
+    @gamma_grad.register_fake
+    def _(x, grad, gamma):
+        return x.new_empty((gamma.numel() if x.shape[0] > 1 else 1,), dtype=torch.float32)
+
+    @define("tio_hip::noise_grad", mutates_args=(), device_types="cuda",
+            schema="(Tensor x, Tensor grad, Tensor mean, Tensor std, bool rician=False, Tensor? base=None, Tensor? base2=None, int philox_seed=0, Tensor? keep=None) -> (Tensor, Tensor)")
+    def noise_grad(x, grad, mean, std, rician=False, base=None, base2=None, philox_seed=0, keep=None):
+        return ops.hip_engine().noise_grad(x, grad, mean, std, rician=rician, base1=base, base2=base2, philox_seed=philox_seed, keep=keep)
+
+    @noise_grad.register_fake
+    def _(x, grad, mean, std, rician=False, base=None, base2=None, philox_seed=0, keep=None):
+        return x.new_empty((mean.numel(),), dtype=torch.float32), x.new_empty((std.numel(),), dtype=torch.float32)
+
+    @define("tio_hip::separable_conv3d_taps_grad", mutates_args=(), device_types="cuda", schema="(Tensor x, Tensor grad, Tensor taps, int[] radius, Tensor? skip=None) -> Tensor")
+    def separable_conv3d_taps_grad(x, grad, taps, radius, skip=None):
+        return ops.hip_engine().separable_conv3d_taps_grad(x, grad, taps, radius, skip=skip)
+
+    @separable_conv3d_taps_grad.register_fake
+    def _(x, grad, taps, radius, skip=None):
+        return taps.new_empty(taps.shape, dtype=torch.float32, device=x.device)
+
+    @define("tio_hip::separable_conv3d_adjoint", mutates_args=(), device_types="cuda", schema="(Tensor grad, Tensor taps, int[] radius, Tensor? skip=None) -> Tensor")
+    def separable_conv3d_adjoint(grad, taps, radius, skip=None):  # (the data's gradient of the stencil, as an op: a traced backward pass can hold it)
+        return ops.hip_engine().separable_conv3d_adjoint(grad, taps, radius, skip=skip)
+
+    @separable_conv3d_adjoint.register_fake
+    def _(grad, taps, radius, skip=None):
+        return grad.new_empty(grad.shape, dtype=torch.float32)
+
+    @define("tio_hip::philox_normal_like", mutates_args=(), device_types="cuda", schema="(Tensor x, int philox_seed, int stream_id) -> Tensor")
+    def philox_normal_like(x, philox_seed, stream_id):
+        return ops.hip_engine().philox_normal(x.shape, philox_seed, stream_id, x.device)
+
+    @philox_normal_like.register_fake
+    def _(x, philox_seed, stream_id):
+        return x.new_empty(x.shape, dtype=torch.float32)
+
+
 def _register_dispatcher_extras() -> None:
     """Fake kernels and autograd formulas of the ``tio_hip`` ops (once, after the library is loaded)."""
     lib = torch.library
+    _define_parameter_gradient_ops()
 
     # ---- shapes / dtypes without a device -------------------------------------------------------------------------
     @lib.register_fake("tio_hip::resample3d")
@@ -162,11 +226,12 @@ def _register_dispatcher_extras() -> None:
         ctx.radius, ctx.skip = list(radius), (inputs[3] if len(inputs) > 3 else None)
 
     def conv_backward(ctx, grad):
-        from . import ops  # noqa: PLC0415
-
         x, taps = ctx.saved_tensors  # (the transposed clamped stencil: tio_separable_conv3d_adjoint, ABI 16)
-        adjoint = ops.hip_engine().separable_conv3d_adjoint(grad, taps.detach(), ctx.radius, skip=ctx.skip)
-        return (adjoint.to(x.dtype), *([None] * (ctx.n_inputs - 1)))
+        adjoint = torch.ops.tio_hip.separable_conv3d_adjoint(grad.contiguous(), taps.detach(), ctx.radius, ctx.skip).to(x.dtype) if ctx.needs_input_grad[0] else None
+        d_taps = None
+        if ctx.needs_input_grad[1]:
+            d_taps = torch.ops.tio_hip.separable_conv3d_taps_grad(x.detach(), grad.float().contiguous(), taps.detach(), ctx.radius, ctx.skip).to(taps.dtype)
+        return (adjoint, d_taps, *([None] * (ctx.n_inputs - 2)))
 
     lib.register_autograd("tio_hip::separable_conv3d", conv_backward, setup_context=conv_setup)
 
@@ -174,9 +239,15 @@ def _register_dispatcher_extras() -> None:
         x, coarse = inputs[:2]
         ctx.n_inputs = len(inputs)
         ctx.coarse, ctx.divide, ctx.skip, ctx.dtype = coarse, bool(inputs[2]) if len(inputs) > 2 else False, (inputs[3] if len(inputs) > 3 else None), x.dtype
+        ctx.x = x.detach() if coarse.requires_grad else None  # the coarse grid's gradient needs the data: kept only when somebody will ask for it
 
     def bias_backward(ctx, grad):  # y = x * f (or x / f): the same multiply applied to the incoming gradient
-        return (torch.ops.tio_hip.bias_field_apply(grad.to(ctx.dtype).contiguous(), ctx.coarse, ctx.divide, ctx.skip), *([None] * (ctx.n_inputs - 1)))
+        coarse = ctx.coarse.detach()
+        d_x = torch.ops.tio_hip.bias_field_apply(grad.to(ctx.dtype).contiguous(), coarse, ctx.divide, ctx.skip) if ctx.needs_input_grad[0] else None
+        d_coarse = None
+        if ctx.needs_input_grad[1]:
+            d_coarse = torch.ops.tio_hip.bias_field_grad(ctx.x, grad.float().contiguous(), coarse, ctx.divide, ctx.skip).to(ctx.coarse.dtype)
+        return (d_x, d_coarse, *([None] * (ctx.n_inputs - 2)))
 
     lib.register_autograd("tio_hip::bias_field_apply", bias_backward, setup_context=bias_setup)
 
@@ -185,16 +256,27 @@ def _register_dispatcher_extras() -> None:
         x, mean, std, rician, base, base2, philox_seed, keep = padded
         ctx.n_inputs = len(inputs)
         ctx.rician = bool(rician)
-        if ctx.rician:
-            if base is None:
-                raise RuntimeError("tio_hip::add_noise: the Rician backward needs the explicit draws (`base`); in-kernel Philox draws are not kept")
-            ctx.save_for_backward(x, output, mean, std, base)
-            ctx.keep = keep
+        ctx.wants_parameters = mean.requires_grad or std.requires_grad
+        ctx.seed, ctx.keep = int(philox_seed or 0), keep
+        ctx.base, ctx.base2 = base, base2
+        if ctx.rician or ctx.wants_parameters:
+            ctx.save_for_backward(x, output, mean, std)
+
+    def noise_parameters(ctx, grad):  # (d_mean, d_std) in the dtypes and on the devices of mean / std, None where not asked for
+        if not any(ctx.needs_input_grad[1:3]):
+            return None, None
+        x, _, mean, std = ctx.saved_tensors
+        computed = torch.ops.tio_hip.noise_grad(x.detach(), grad.float().contiguous(), mean.detach(), std.detach(), ctx.rician, ctx.base, ctx.base2,
+                                                ctx.seed, ctx.keep)
+        return tuple(value.reshape(like.shape).to(device=like.device, dtype=like.dtype) if wanted else None
+                     for value, like, wanted in zip(computed, (mean, std), ctx.needs_input_grad[1:3], strict=True))
 
     def noise_backward(ctx, grad):
         if not ctx.rician:  # additive: dy/dx = 1 (gated-out rows are copies: 1 as well)
-            return (grad, *([None] * (ctx.n_inputs - 1)))
-        x, y, mean, std, base = ctx.saved_tensors
+            return (grad, *noise_parameters(ctx, grad), *([None] * (ctx.n_inputs - 3)))
+        x, y, mean, std = ctx.saved_tensors
+        mean, std = mean.detach().to(x.device), std.detach().to(x.device)
+        base = ctx.base if ctx.base is not None else torch.ops.tio_hip.philox_normal_like(x, ctx.seed, 0)  # (the draws are regenerated)
         shape = (-1,) + (1,) * (x.ndim - 1)
         mean_b = mean.reshape(shape) if mean.numel() > 1 else mean
         std_b = std.reshape(shape) if std.numel() > 1 else std
@@ -202,7 +284,7 @@ def _register_dispatcher_extras() -> None:
         slope = torch.where(y != 0, numerator / y.float(), torch.zeros_like(numerator))
         if ctx.keep is not None:
             slope = torch.where(ctx.keep.bool().reshape(shape), slope, torch.ones_like(slope))
-        return ((grad.float() * slope).to(x.dtype), *([None] * (ctx.n_inputs - 1)))
+        return ((grad.float() * slope).to(x.dtype), *noise_parameters(ctx, grad), *([None] * (ctx.n_inputs - 3)))
 
     lib.register_autograd("tio_hip::add_noise", noise_backward, setup_context=noise_setup)
 
@@ -212,8 +294,15 @@ def _register_dispatcher_extras() -> None:
 
     def gamma_backward(ctx, grad):  # y = sign(x) |x|^g: dy/dx = g |x|^(g - 1)
         x, gamma = ctx.saved_tensors
-        exponent = gamma.to(x.device, torch.float32).reshape((-1,) + (1,) * (x.ndim - 1)) if gamma.numel() > 1 else gamma.to(x.device, torch.float32)
-        return (grad.float() * exponent * x.float().abs().pow(exponent - 1)).to(x.dtype), None
+        d_x = d_gamma = None
+        if ctx.needs_input_grad[0]:
+            values = gamma.detach()
+            exponent = values.to(x.device, torch.float32).reshape((-1,) + (1,) * (x.ndim - 1)) if values.numel() > 1 else values.to(x.device, torch.float32)
+            d_x = (grad.float() * exponent * x.float().abs().pow(exponent - 1)).to(x.dtype)
+        if ctx.needs_input_grad[1]:
+            d_gamma = torch.ops.tio_hip.gamma_grad(x.detach(), grad.float().contiguous(), gamma.detach())
+            d_gamma = d_gamma.reshape(gamma.shape).to(device=gamma.device, dtype=gamma.dtype)
+        return d_x, d_gamma
 
     lib.register_autograd("tio_hip::gamma_pow", gamma_backward, setup_context=gamma_setup)
 
