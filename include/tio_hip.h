@@ -594,6 +594,42 @@ int tio_pad3d(const void* x, void* y, int32_t dtype, int32_t batch, int32_t chan
               const int32_t in_shape[3], const int32_t padding[6], int32_t mode, double fill,
               const void* fill_per_element_dev, void* stream);
 
+/*
+ * The transposes of three of the data movers above (additive to ABI 18, HIP only): what autograd derives for the image
+ * through the reference's F.interpolate / gather / F.pad calls.  Gradients are float32 in and out.  Each is a GATHER:
+ * one thread per element of gx, every element of gx written exactly once (no atomics, the caller need not zero it), the
+ * additions of an element in a fixed order - two calls give the same bits.  gx must not alias gy.
+ *
+ * tio_interpolate3d_adjoint: gy (N, out_shape) -> gx (N, in_shape), the transpose of tio_interpolate3d for TIO_LINEAR
+ *   (trilinear, align_corners=True: resize.py:70-76, anisotropy.py:386-391) and TIO_NEAREST (the legacy "nearest":
+ *   resize.py:70-76, anisotropy.py:380-384).  Per axis the outputs that read an input index form one contiguous range; its
+ *   ends and the weights come from the forward's own float32 index expressions, the product of the three weights is
+ *   rounded in the forward's order (K, J, I).  An input no output reads (down-sampling) receives 0.  No axis longer than
+ *   2^21 voxels on either side (the closed-form range ends are proven up to there): TIO_ERR_INVALID_ARGUMENT beyond.
+ *
+ * tio_axis_gather_lerp_adjoint: the transpose of tio_axis_gather_lerp (_simulate_anisotropy_fixed_axis,
+ *   anisotropy.py:180-208).  The caller inverts the (B, length) tables into per-element lists:
+ *     offsets_dev    int32 (B, length + 1): entries [offsets[b, p], offsets[b, p + 1]) of element b read source index p
+ *     positions_dev  int32 (B, entries): the output position along the axis of each entry
+ *     weights_dev    float32 (B, entries): its weight (1 - w for a `lower` entry, w for an `upper` one, each as the
+ *                    forward forms it), or NULL: every weight is 1 (nearest)
+ *   gx[b, c, .., p, ..] = sum over p's entries of gy[.., position, ..] * weight, in list order.  Offsets and positions
+ *   are clamped to the element's list and line.  active_dev (B bytes or NULL): 0 = gx is a copy of gy for that element.
+ *
+ * tio_pad3d_adjoint: gy (B, C, in_shape + padding) -> gx (B, C, in_shape), the transpose of tio_pad3d
+ *   (_padding.py:62-104) for TIO_PAD_REFLECT / TIO_PAD_REPLICATE / TIO_PAD_CIRCULAR under tio_pad3d's own limits: along
+ *   an axis an index receives its own position plus at most one border position per side (reflect, circular) or the whole
+ *   border run (replicate, first and last index); the three axes' position sets multiply.  TIO_PAD_CONSTANT: refused
+ *   (its transpose is a crop).
+ */
+int tio_interpolate3d_adjoint(const float* gy, float* gx, int64_t n_batch_channels, const int32_t in_shape[3],
+                              const int32_t out_shape[3], int32_t mode, void* stream);
+int tio_axis_gather_lerp_adjoint(const float* gy, float* gx, int32_t batch, int32_t channels, const int32_t shape[3],
+                                 int32_t axis, const int32_t* offsets_dev, const int32_t* positions_dev,
+                                 const float* weights_dev, int32_t entries, const uint8_t* active_dev, void* stream);
+int tio_pad3d_adjoint(const float* gy, float* gx, int32_t batch, int32_t channels, const int32_t in_shape[3],
+                      const int32_t padding[6], int32_t mode, void* stream);
+
 /* ------------------------------------------------------------------------ */
 /* Feeding side: dense-inference patch aggregation        */
 /* ------------------------------------------------------------------------ */

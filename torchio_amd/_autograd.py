@@ -19,6 +19,21 @@ class _AttachBackward(torch.autograd.Function):
         return ctx.backward_fn(grad.contiguous()), None, None
 
 
+class _AttachBackwardMany(torch.autograd.Function):
+    """``_AttachBackward`` for a kernel with several data inputs (Motion's k-space composite): ``result`` was computed from the
+    detached ``sources``; ``backward_fn(grad, needs)`` returns one gradient (or ``None``) per source, ``needs[n]`` telling which
+    are wanted."""
+
+    @staticmethod
+    def forward(ctx, backward_fn, result, *sources):
+        ctx.backward_fn = backward_fn
+        return result.view_as(result)
+
+    @staticmethod
+    def backward(ctx, grad):
+        return (None, None, *ctx.backward_fn(grad.contiguous(), ctx.needs_input_grad[2:]))
+
+
 class _AttachGeometryBackward(torch.autograd.Function):
     """Give the results of one resampling call their dependence on its geometry: ``results`` were computed by a kernel from the
     detached ``mapping`` / ``control_points`` (the leaves, or what leads to them); ``backward_fn(grads, want_mapping,

@@ -276,12 +276,18 @@ extern "C" int tio_kspace_mix_table(int32_t length, int32_t n_segments, const in
   const double step = 2.0 * M_PI / static_cast<double>(length);
   for (int s = 0; s < n_segments; s++) {
     float* block = table_host + static_cast<int64_t>(s) * length * length;
-    for (int d = 0; d < length; d++) {  // the circulant's generator: value at (i - i') mod I == d
+    for (int d = 0; d <= length / 2; d++) {  // the circulant's generator: value at (i - i') mod I == d
       double sum = 0.0;
       for (int f = bounds[s]; f < bounds[s + 1]; f++)
         sum += cos(step * static_cast<double>((static_cast<int64_t>(f) * d) % length));
       const float value = static_cast<float>(sum / static_cast<double>(length));
-      for (int ip = 0; ip < length; ip++) block[static_cast<int64_t>(ip) * length + (ip + d) % length] = value;
+      // cos is even: the value at I - d is the same number.  It is WRITTEN as the same bits (summed on its own, cos(2 pi - t)
+      // differs from cos(t) in the last float64 bit, which shows where a sum cancels to zero), so every block equals its
+      // transpose bit for bit - the backward of the mix applies the block itself (ops.Engine.kspace_segment_mix).
+      for (int ip = 0; ip < length; ip++) {
+        block[static_cast<int64_t>(ip) * length + (ip + d) % length] = value;
+        block[static_cast<int64_t>(ip) * length + (ip + length - d) % length] = value;
+      }
     }
   }
   return TIO_OK;

@@ -25,6 +25,7 @@ from . import _lib
 # The side streams (streams.py) and the reference's noise stream (noise_stream.py) are modules of their own; their public
 # names — and the error type and autograd helpers they share with the engine — are read through `ops` as well.
 from ._autograd import _AttachBackward
+from ._autograd import _AttachBackwardMany
 from ._autograd import _AttachGeometryBackward
 from ._autograd import _AttachParameterBackward
 from ._autograd import _wants_grad
@@ -239,6 +240,9 @@ class Engine:
     parameters of the intensity ops: a coarse bias grid, blur taps, a noise mean / deviation or a gamma exponent that requires a
     gradient receives one from the fused reductions of ``intensity_param_grad.hip`` (``bias_field_grad``, ``separable_conv3d_taps_grad``,
     ``noise_grad``, ``gamma_grad``); plain numbers get none.
+    The pre-processing ops are linear in the data and attach their transposes: the gather adjoints of ``interpolate_adjoint.hip`` for
+    ``interpolate3d``, ``axis_gather_lerp`` and the reflect / replicate / circular ``pad3d``; ``ghost_lines`` and ``kspace_segment_mix`` are
+    symmetric operators and run their own kernel on the gradient.
     """
 
     def __init__(self, functions: dict, device_type: str, name: str):
@@ -260,7 +264,8 @@ class Engine:
             if t.requires_grad and torch.is_grad_enabled():  # (with grad disabled a tensor that requires grad is just data)
                 raise EngineError(
                     f"{what}: this {self.name} engine op has no backward (differentiable: trilinear resampling, bias field, blur,"
-                    " noise, gamma, flip) — detach the tensor, or use `torchio` with `torchio_amd.reference_binding.bind()`,"
+                    " noise, gamma, flip, permute, pad, interpolate3d, axis_gather_lerp, ghost_lines, kspace_segment_mix) — detach"
+                    " the tensor, or use `torchio` with `torchio_amd.reference_binding.bind()`,"
                     " which leaves autograd inputs to the reference's own path"
                 )
 
@@ -296,6 +301,13 @@ class Engine:
             raise NotImplementedError(
                 f"{what} requires a gradient, but the {self.name} engine has no tio_{name}: the parameter gradients of the intensity"
                 " ops exist on the HIP engine only - detach the parameter, or run on the GPU")
+
+    def _data_adjoint_kernel(self, name: str, what: str) -> None:
+        """The gather adjoints of ``interpolate_adjoint.hip`` (``tio_<name>``): only the HIP library has them."""
+        if name not in self._fn:
+            raise NotImplementedError(
+                f"{what}: the {self.name} engine has no tio_{name}: the data gradients of interpolate3d, axis_gather_lerp and the"
+                " reflect / replicate / circular pad3d exist on the HIP engine only - detach the tensor, or run on the GPU")
 
     def _workspace(self, name: str, ref: Tensor, *args) -> tuple[Tensor, int]:
         nbytes = int(self._fn[name](*args))
@@ -1089,6 +1101,11 @@ class Engine:
         """``F.interpolate(data.float(), size=out_shape, mode).to(data.dtype)``: ``"nearest"`` or ``"linear"`` (trilinear, align_corners)."""
         if data.ndim != 5:
             raise ValueError(f"expected a (B, C, I, J, K) tensor, got {tuple(data.shape)}")
+        if _wants_grad(data) and mode in ("nearest", "linear"):  # linear in the data: the backward is its transpose, a gather
+            self._data_adjoint_kernel("interpolate3d_adjoint", "interpolate3d: the data requires a gradient")
+            result = self.interpolate3d(data.detach(), out_shape, mode)
+            in_shape = tuple(data.shape[2:])
+            return _AttachBackward.apply(data, result, lambda grad: self.interpolate3d_adjoint(grad, in_shape, mode).to(data.dtype))
         data = data.contiguous()
         self._check("interpolate3d", data)
         out_shape = tuple(int(s) for s in out_shape)
@@ -1097,6 +1114,22 @@ class Engine:
             "interpolate3d", data, _ptr(data), _ptr(out), dtype_code(data.dtype), data.shape[0] * data.shape[1],
             _i32x3(data.shape[2:]), _i32x3(out_shape), INTERP_CODES[mode], self._stream(data),
         )
+        return out
+
+    def interpolate3d_adjoint(self, grad: Tensor, in_shape: Sequence[int], mode: str) -> Tensor:
+        """The transpose of ``interpolate3d(., grad.shape[2:], mode)`` applied to *grad* ``(B, C, *out_shape)``: dL/d(input),
+        float32 ``(B, C, *in_shape)`` (``tio_interpolate3d_adjoint``: one thread per input voxel, no atomics, reproducible)."""
+        if grad.ndim != 5:
+            raise ValueError(f"expected a (B, C, I, J, K) gradient, got {tuple(grad.shape)}")
+        if mode not in ("nearest", "linear"):
+            raise ValueError(f'interpolate3d_adjoint: mode must be "nearest" or "linear", got {mode!r}')
+        self._data_adjoint_kernel("interpolate3d_adjoint", "interpolate3d_adjoint")
+        grad = grad.to(torch.float32).contiguous()
+        self._check("interpolate3d_adjoint", grad)
+        in_shape = tuple(int(s) for s in in_shape)
+        out = torch.empty((*grad.shape[:2], *in_shape), dtype=torch.float32, device=grad.device)
+        self._call("interpolate3d_adjoint", grad, _ptr(grad), _ptr(out), grad.shape[0] * grad.shape[1], _i32x3(in_shape),
+                   _i32x3(grad.shape[2:]), INTERP_CODES[mode], self._stream(grad))
         return out
 
     def axis_gather_lerp(self, data: Tensor, axis: int, lower: Tensor, upper: Tensor | None = None,
@@ -1119,12 +1152,65 @@ class Engine:
         active = self._flags(active, batch, "active")
         if active is not None:
             active = h2d(active, data.device)
+        if _wants_grad(data):  # linear in the data: the backward gathers along the inverted tables (already on the device)
+            self._data_adjoint_kernel("axis_gather_lerp_adjoint", "axis_gather_lerp: the data requires a gradient")
+            result = self.axis_gather_lerp(data.detach(), axis, lower, upper, weight, active)
+            return _AttachBackward.apply(
+                data, result, lambda grad: self.axis_gather_lerp_adjoint(grad, axis, lower, upper, weight, active).to(data.dtype))
         self._check("axis_gather_lerp", data, lower, upper, weight, active)
         out = torch.empty_like(data)
         self._call(
             "axis_gather_lerp", data, _ptr(data), _ptr(out), dtype_code(data.dtype), batch, data.shape[1], _i32x3(data.shape[2:]),
             int(axis), _ptr(lower), _ptr(upper), _ptr(weight), _ptr(active), self._stream(data),
         )
+        return out
+
+    @staticmethod
+    def axis_gather_lists(lower: Tensor, upper: Tensor | None = None, weight: Tensor | None = None) -> tuple[Tensor, Tensor, Tensor | None]:
+        """The ``(B, length)`` tables of ``axis_gather_lerp`` inverted into one list per source index, with torch ops on the
+        tables' own device and no read-back: ``offsets`` int32 ``(B, length + 1)``, ``positions`` int32 ``(B, E)`` and
+        ``weights`` float32 ``(B, E)`` (``None`` for the nearest form), ``E = length`` or ``2 * length``.  The entries
+        ``offsets[b, p] .. offsets[b, p + 1]`` of element ``b`` are the outputs that read source ``p``: the ``lower`` uses by
+        ascending position with the weight ``1 - w`` (rounded as the forward rounds it), then the ``upper`` uses with ``w``
+        (a stable sort by source).  Entries whose source lies outside ``[0, length)`` belong to no list."""
+        batch, length = lower.shape
+        positions = torch.arange(length, dtype=torch.int32, device=lower.device)
+        if upper is None:
+            sources, positions, weights = lower, positions.expand(batch, length), None
+        else:
+            sources = torch.cat([lower, upper], dim=1)
+            positions = torch.cat([positions, positions]).expand(batch, 2 * length)
+            weights = torch.cat([1.0 - weight, weight], dim=1)
+        sources, order = torch.sort(sources.to(torch.int32), dim=1, stable=True)
+        ends = torch.arange(length + 1, dtype=torch.int32, device=lower.device).expand(batch, length + 1).contiguous()
+        offsets = torch.searchsorted(sources.contiguous(), ends, out_int32=True)
+        positions = positions.gather(1, order).contiguous()
+        return offsets.contiguous(), positions, None if weights is None else weights.gather(1, order).contiguous()
+
+    def axis_gather_lerp_adjoint(self, grad: Tensor, axis: int, lower: Tensor, upper: Tensor | None = None,
+                                 weight: Tensor | None = None, active: Tensor | None = None) -> Tensor:
+        """The transpose of ``axis_gather_lerp(., axis, lower, upper, weight, active)`` applied to *grad*: dL/d(input), float32
+        (``tio_axis_gather_lerp_adjoint`` over the lists of ``axis_gather_lists``; inactive elements pass *grad* on)."""
+        if grad.ndim != 5:
+            raise ValueError(f"expected a (B, C, I, J, K) gradient, got {tuple(grad.shape)}")
+        self._data_adjoint_kernel("axis_gather_lerp_adjoint", "axis_gather_lerp_adjoint")
+        grad = grad.to(torch.float32).contiguous()
+        batch, length = grad.shape[0], grad.shape[2 + axis]
+        tables = [None if t is None else h2d(t.to(dtype).contiguous(), grad.device)
+                  for t, dtype in ((lower, torch.int32), (upper, torch.int32), (weight, torch.float32))]
+        for t in tables:
+            if t is not None and tuple(t.shape) != (batch, length):
+                raise ValueError(f"index / weight tables must be (B, length) = {(batch, length)}, got {tuple(t.shape)}")
+        if tables[1] is not None and tables[2] is None:
+            raise ValueError("axis_gather_lerp_adjoint: upper without weights")
+        active = self._flags(active, batch, "active")
+        if active is not None:
+            active = h2d(active, grad.device)
+        offsets, positions, weights = self.axis_gather_lists(*tables)
+        self._check("axis_gather_lerp_adjoint", grad, offsets, positions, weights, active)
+        out = torch.empty_like(grad)
+        self._call("axis_gather_lerp_adjoint", grad, _ptr(grad), _ptr(out), batch, grad.shape[1], _i32x3(grad.shape[2:]), int(axis),
+                   _ptr(offsets), _ptr(positions), _ptr(weights), positions.shape[1], _ptr(active), self._stream(grad))
         return out
 
     def flip3d(self, data: Tensor, axes: Sequence[int] | None = None, per_element: Tensor | None = None) -> Tensor:
@@ -1186,9 +1272,16 @@ class Engine:
             raise ValueError(f"expected a (B, C, I, J, K) tensor, got {tuple(data.shape)}")
         code = {"constant": _abi.PAD_CONSTANT, "reflect": _abi.PAD_REFLECT, "replicate": _abi.PAD_REPLICATE, "circular": _abi.PAD_CIRCULAR}[mode]
         if _wants_grad(data) or _wants_grad(fill_per_element):
-            if mode != "constant":
-                raise EngineError(f"pad3d: mode {mode!r} has no backward in the {self.name} engine (constant / statistic padding does)")
-            return _PadConstantFn.apply(data, fill_per_element, self, [int(p) for p in padding], float(fill))
+            if mode == "constant":
+                return _PadConstantFn.apply(data, fill_per_element, self, [int(p) for p in padding], float(fill))
+            if not _wants_grad(data):
+                raise EngineError(f"pad3d: fill values take no part in mode {mode!r}, they have no gradient there (constant / statistic padding)")
+            # the border repeats voxels of the image: the backward folds it back onto them (a gather per input voxel)
+            self._data_adjoint_kernel("pad3d_adjoint", f"pad3d: the data requires a gradient through mode {mode!r}")
+            fills = None if fill_per_element is None else fill_per_element.detach()
+            result = self.pad3d(data.detach(), padding, mode, fill, fills)
+            in_shape, padding = tuple(data.shape[2:]), [int(p) for p in padding]
+            return _AttachBackward.apply(data, result, lambda grad: self.pad3d_adjoint(grad, in_shape, padding, mode).to(data.dtype))
         data = data.contiguous()
         padding = [int(p) for p in padding]
         if len(padding) != 6:
@@ -1203,6 +1296,27 @@ class Engine:
         out = torch.empty((*data.shape[:2], *shape), dtype=data.dtype, device=data.device)
         self._call("pad3d", data, _ptr(data), _ptr(out), dtype_code(data.dtype), data.shape[0], data.shape[1], _i32x3(data.shape[2:]),
                    (C.c_int32 * 6)(*padding), code, float(fill), _ptr(fills), self._stream(data))
+        return out
+
+    def pad3d_adjoint(self, grad: Tensor, in_shape: Sequence[int], padding: Sequence[int], mode: str) -> Tensor:
+        """The transpose of ``pad3d(., padding, mode)`` for ``"reflect"`` / ``"replicate"`` / ``"circular"`` applied to *grad*
+        ``(B, C, *(in_shape + padding))``: dL/d(input), float32 ``(B, C, *in_shape)`` (``tio_pad3d_adjoint``)."""
+        if grad.ndim != 5:
+            raise ValueError(f"expected a (B, C, I, J, K) gradient, got {tuple(grad.shape)}")
+        if mode not in ("reflect", "replicate", "circular"):
+            raise ValueError(f'pad3d_adjoint: mode must be "reflect", "replicate" or "circular", got {mode!r}')
+        code = {"reflect": _abi.PAD_REFLECT, "replicate": _abi.PAD_REPLICATE, "circular": _abi.PAD_CIRCULAR}[mode]
+        in_shape, padding = [int(s) for s in in_shape], [int(p) for p in padding]
+        if len(padding) != 6:
+            raise ValueError("padding must have 6 values (i0, i1, j0, j1, k0, k1)")
+        if [in_shape[d] + padding[2 * d] + padding[2 * d + 1] for d in range(3)] != list(grad.shape[2:]):
+            raise ValueError(f"pad3d_adjoint: a gradient of {tuple(grad.shape[2:])} is not {tuple(in_shape)} padded by {tuple(padding)}")
+        self._data_adjoint_kernel("pad3d_adjoint", "pad3d_adjoint")
+        grad = grad.to(torch.float32).contiguous()
+        self._check("pad3d_adjoint", grad)
+        out = torch.empty((*grad.shape[:2], *in_shape), dtype=torch.float32, device=grad.device)
+        self._call("pad3d_adjoint", grad, _ptr(grad), _ptr(out), grad.shape[0], grad.shape[1], _i32x3(in_shape),
+                   (C.c_int32 * 6)(*padding), code, self._stream(grad))
         return out
 
     def unique_labels(self, data: Tensor) -> Tensor:
@@ -1699,6 +1813,10 @@ class Engine:
         """
         if data.ndim != 5:
             raise ValueError(f"ghost_lines: expected a (B, C, I, J, K) tensor, got {tuple(data.shape)}")
+        if _wants_grad(data):  # per line x - (strength / S) sum_f (c_f c_f^T + s_f s_f^T) x: a symmetric matrix, its own transpose
+            result = self.ghost_lines(data.detach(), axes, strengths, frequency_lists, active)
+            return _AttachBackward.apply(
+                data, result, lambda grad: self.ghost_lines(grad.to(torch.float32), axes, strengths, frequency_lists, active).to(data.dtype))
         batch, shape = int(data.shape[0]), [int(s) for s in data.shape[2:]]
         axes = [int(a) for a in self._per_element(axes, batch, "ghost_lines: axes")]
         strengths = [float(s) for s in self._per_element(strengths, batch, "ghost_lines: strengths")]
@@ -1817,6 +1935,8 @@ class Engine:
             raise ValueError(f"at most {_abi.MAX_SEGMENTS - 1} motion transforms are supported, got {len(segments) - 1}")
         if len(bounds) != len(segments) + 1:
             raise ValueError("bounds must have one more entry than segments")
+        if any(_wants_grad(s) for s in segments):
+            return self._segment_mix_with_backward(list(segments), [int(v) for v in bounds], out_dtype, active)
         segments = [s.contiguous() for s in segments]
         for s in segments:
             if s.dtype != torch.float32 or s.shape != first.shape:
@@ -1826,11 +1946,44 @@ class Engine:
         table = self._mix_table(length, tuple(int(v) for v in bounds), first.device)
         flags = None if active is None else active.to(torch.uint8).contiguous()
         out = torch.empty(first.shape, dtype=out_dtype, device=first.device)
+        self._segment_mix_launch(segments, bounds, table, out, flags)
+        return out
+
+    def _segment_mix_launch(self, segments: Sequence[Tensor], bounds: Sequence[int], table: Tensor, out: Tensor, flags: Tensor | None) -> None:
+        first = segments[0]
         pointers = (C.c_void_p * len(segments))(*[s.data_ptr() for s in segments])
         self._call("kspace_segment_mix", first, pointers, len(segments), (C.c_int32 * len(bounds))(*[int(v) for v in bounds]),
-                   _ptr(table), _ptr(out), dtype_code(out_dtype), first.shape[0], first.shape[1], _i32x3(first.shape[2:]),
+                   _ptr(table), _ptr(out), dtype_code(out.dtype), first.shape[0], first.shape[1], _i32x3(first.shape[2:]),
                    _ptr(flags), self._stream(first))
-        return out
+
+    def _segment_mix_with_backward(self, segments: list[Tensor], bounds: list[int], out_dtype: torch.dtype, active: Tensor | None) -> Tensor:
+        """``kspace_segment_mix`` of segments that require gradients.  The launch evaluates ``out = x_0 + sum_{s >= 1} W[s]
+        (x_s - x_0)`` and ``W[s][i'][i]`` depends on ``i - i'`` through a cosine only: every ``W[s]`` is symmetric, so
+        ``dL/dx_s = W[s] g`` and ``dL/dx_0 = g - sum_{s >= 1} W[s] g`` are launches of the same kernel on the gradient — with the
+        zero volume as the still image and ``W[s]`` as the only moved block, and with the gradient as the still image and the
+        zero volume moved everywhere.  Rows of inactive elements receive zero (the launch skips them both ways)."""
+        result = self.kspace_segment_mix([s.detach() for s in segments], bounds, out_dtype, active)
+        length, device = int(result.shape[2]), result.device
+        flags = None if active is None else active.to(torch.uint8).contiguous()
+
+        def backward(grad, needs):
+            grad = grad.to(torch.float32).contiguous()
+            self._check("kspace_segment_mix (backward)", grad)
+            table = self._mix_table(length, tuple(bounds), device)
+            zero = torch.zeros_like(grad)
+            grads: list[Tensor | None] = [None] * len(segments)
+            for s, need in enumerate(needs):
+                if not need:
+                    continue
+                # (rows of inactive elements are not written by the launch: they start, and stay, at zero)
+                grads[s] = torch.zeros_like(grad) if flags is not None else torch.empty(grad.shape, dtype=torch.float32, device=grad.device)
+                if s == 0:
+                    self._segment_mix_launch([grad] + [zero] * (len(segments) - 1), bounds, table, grads[s], flags)
+                else:  # the kernel reads block 1 of the table it is given: hand it the blocks s - 1 and s
+                    self._segment_mix_launch([zero, grad], [0, 0, length], table[s - 1 : s + 1], grads[s], flags)
+            return grads
+
+        return _AttachBackwardMany.apply(backward, result, *segments)
 
     def _mix_table(self, length: int, bounds: tuple, device) -> Tensor:
         """The ``(n_segments, I, I)`` band-pass table of ``tio_kspace_segment_mix`` on *device* (built once per shape)."""

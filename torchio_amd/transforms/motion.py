@@ -104,6 +104,9 @@ def _apply_motion_per_instance(data: Tensor, motion_transforms) -> Tensor:
     transformed = _apply_motion_segments(data, segments, active=None if all(active) else torch.tensor(active))
     if all(active):
         return transformed
+    if transformed.requires_grad:  # autograd takes no in-place write into an engine result: the same restore, out of place
+        keep = ops.h2d(torch.tensor(active), data.device).view(-1, 1, 1, 1, 1)
+        return torch.where(keep, transformed, data)
     inactive = ops.h2d(torch.tensor([i for i, a in enumerate(active) if not a]), data.device)
     transformed.index_copy_(0, inactive, data.index_select(0, inactive))  # rows restored exactly from the input
     return transformed
